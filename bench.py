@@ -24,6 +24,10 @@ ms/step), "other_workloads": the same measurement, compact, for the other two si
 "next_rows": the rows SURVEY.md 8 marks "next" that have a measurement of their own -- the ndsp PSK demodulator chain
 (tools/bench_ndsp.py), the DVB-S2 FEC tail (tools/bench_dvbs2.py) and BASELINE configs[4] itself, 8PSK baseband -> BBFRAMEs through the module-shaped
 handle (tools/bench_dvbs2_demod.py), the Meteor LRPT decoder (tools/bench_lrpt.py), the FengYun-3 AHRPT decoder (tools/bench_fy3.py) -- as those tools report them (--next-rows 0 to skip).
+
+All of these but "roofline" and "kernels" (HIP-event times of the timed steps themselves), and the "check" of the last step's CADUs against the transmitted
+frames, are taken under --full only. A plain run synthesises the input, warms up, times --steps steps, writes the last step's outputs if --dump-outputs DIR
+is given, and prints the line.
 """
 from __future__ import annotations
 
@@ -418,10 +422,18 @@ def main():
                          "recording that --gpus N shards")
     ap.add_argument("--dump", default="", help="write the last step's CADUs of every rank to <prefix>.rank<r>.npy (+ <prefix>.json on rank 0): tests")
     ap.add_argument("--detail", default="", help="where the full result object goes (default: bench_detail.json beside bench.py); stdout carries the compact line only")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline, parity and exact-mode legs, the streamed leg, the other workloads, the next rows "
+                         "and the check of the last step's CADUs against the transmitted frames (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step (rank 0) to DIR/*.npy as float32 / float64: a seeded sample of the soft symbols "
+                         "and of the CADUs, where they sit, and the counts -- for comparing two builds output for output")
     ap.add_argument("--pipeline", action="store_true",
                     help="N=1: overlap the decoder of step i with the demodulator of step i+1 (two host threads, two HIP streams) like the reference's "
                          "thread-per-module pipeline; off by default: the per-kernel HIP-event times of the roofline need the kernels un-overlapped")
     args = ap.parse_args()
+    if args.dump and not args.full:
+        ap.error("--dump is written by the check of the last step: it needs --full")
 
     import torch
     import torch.distributed as dist
@@ -445,12 +457,12 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
     ctx = dict(world=world, rank=rank, local_rank=local_rank, device=device, share_gpu=share_gpu)
 
-    out = run_workload(args, args.workload, args.steps, args.warmup, args.parity_samples, ctx)
+    out = run_workload(args, args.workload, args.steps, args.warmup, args.parity_samples, ctx, dump_dir=args.dump_outputs)
     def _bad(o):
         return bool(o and ((o.get("cadu_parity") is not None and not o["cadu_parity"]["byte_identical"]) or (o.get("parity_gates") is not None and not o["parity_gates"]["passed"])
                            or (o.get("exact_mode") is not None and not o["exact_mode"]["bit_identical_to_the_reference"])))
     failed = _bad(out)
-    if rank == 0 and world == 1 and args.others and not args.exact and not args.frames and not args.dump:
+    if rank == 0 and world == 1 and args.full and args.others and not args.exact and not args.frames and not args.dump:
         # the other two single-GPU workloads, compact: fewer steps, a bounded reference span (GOES' 2 GiB fits it whole)
         others = {}
         for name in WORKLOADS:
@@ -470,7 +482,7 @@ def main():
             others[name] = c
             failed = failed or _bad(o)
         out["other_workloads"] = others
-    if rank == 0 and world == 1 and args.next_rows and not args.exact and not args.frames and not args.dump:
+    if rank == 0 and world == 1 and args.full and args.next_rows and not args.exact and not args.frames and not args.dump:
         # the rows SURVEY.md 8 marks "next", each measured by its own tool (same HIP-event + reference-on-the-host method), compact: the ndsp
         # PSK demodulator chain (f-1) and the DVB-S2 FEC tail (f-2). A failure here is recorded, it never takes the driver line down.
         nxt = {}
@@ -506,8 +518,30 @@ def main():
         dist.destroy_process_group()
 
 
-def run_workload(args, workload, n_steps, n_warmup, parity_samples, ctx):
-    """One measurement of one workload (see the module docstring); returns the result object on rank 0."""
+DUMP_SOFT_RUNS, DUMP_SOFT_LEN, DUMP_CADUS = 64, 1 << 16, 4096  # 16 MB + 16 MB of float32
+
+
+def dump_outputs(dump_dir, d_soft, ns, d_cadu, nf):
+    """--dump-outputs: what a caller of the timed path received from its last step -- the int8 soft symbols d_soft[:ns] and the CADUs d_cadu[:nf] -- as .npy
+    files under 64 MB in all: soft.npy = DUMP_SOFT_RUNS runs of DUMP_SOFT_LEN consecutive soft symbols from seeded positions (soft_at.npy), cadus.npy =
+    DUMP_CADUS whole CADUs at seeded rows (cadu_rows.npy), counts.npy = (ns, nf). The inputs are a function of the arguments, the positions of the counts:
+    two builds run with the same arguments compare file for file."""
+    import torch
+    os.makedirs(dump_dir, exist_ok=True)
+    rng = np.random.default_rng(1234)
+    ln = min(DUMP_SOFT_LEN, ns)
+    at = np.sort(rng.integers(0, ns - ln + 1, size=DUMP_SOFT_RUNS))
+    soft = d_soft[torch.from_numpy(at[:, None] + np.arange(ln)[None, :]).to(d_soft.device)].to(torch.float32).cpu().numpy()
+    rows = np.sort(rng.choice(nf, size=min(DUMP_CADUS, nf), replace=False))
+    cadus = d_cadu[torch.from_numpy(rows).to(d_cadu.device)].to(torch.float32).cpu().numpy()
+    for name, a in (("soft", soft), ("soft_at", at.astype(np.float64)), ("cadus", cadus), ("cadu_rows", rows.astype(np.float64)),
+                    ("counts", np.array([ns, nf], dtype=np.float64))):
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
+def run_workload(args, workload, n_steps, n_warmup, parity_samples, ctx, dump_dir=""):
+    """One measurement of one workload (see the module docstring); returns the result object on rank 0. dump_dir: where rank 0 writes
+    the last timed step's outputs (dump_outputs)."""
     import torch
     import torch.distributed as dist
     from satdump_amd import capi, shard, synth
@@ -552,7 +586,7 @@ def run_workload(args, workload, n_steps, n_warmup, parity_samples, ctx):
 
     # ---- parity leg, part 1 (rank 0, N=1): the FIRST pass of fresh handles over the full-size stream, with the float symbols of
     # the prefix the CPU leg will cover. Untimed; it also is the pass that allocates and acquires lock.
-    do_cpu = world == 1 and args.cpu_samples > 0 and not args.exact
+    do_cpu = args.full and world == 1 and args.cpu_samples > 0 and not args.exact
     parity_gpu = None
     warmup_ms = []
     if do_cpu:
@@ -660,6 +694,7 @@ def run_workload(args, workload, n_steps, n_warmup, parity_samples, ctx):
     capi.prof_enable(True)
     pipelined = args.pipeline and n_steps > 1 and world == 1
     t0 = time.perf_counter()
+    last_soft = d_soft
     if not pipelined:
         for _ in range(n_steps):
             ns, nf = step()
@@ -693,11 +728,14 @@ def run_workload(args, workload, n_steps, n_warmup, parity_samples, ctx):
             tot_soft += res["ns", i]
             tot_frames += res["nf", i]
         ns, nf = res["ns", n_steps - 1], res["nf", n_steps - 1]
+        last_soft = bufs[(n_steps - 1) % 2]
     barrier()
     dt = time.perf_counter() - t0
     capi.prof_enable(False)
     prof = capi.prof_get()
     last_nf = nf
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last_soft, ns, d_cadu, nf)
 
     # samples of the recording each rank OWNS (the overlap is re-processed work, not throughput)
     own = float((plan["stop"] - plan["own_start"]) * n_steps)
@@ -706,7 +744,7 @@ def run_workload(args, workload, n_steps, n_warmup, parity_samples, ctx):
     # ---- correctness of what was timed: every CADU of the last step must be one of the transmitted frames of this rank's
     # range (its block plus, with N>1, the overlap frames in front of it); N>1: the stitched list has no duplicates and no gaps
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         got = d_cadu[:last_nf].cpu().numpy()
         want, want_payload = set(), set()
         order = {}

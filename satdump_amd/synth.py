@@ -90,17 +90,37 @@ def rs_generator(nroots=32, fcr=112, gap=11):
     return g  # len nroots+1, g[0] == 1
 
 
-def rs_encode(msgs: np.ndarray, nroots=32) -> np.ndarray:
-    """Systematic RS(255, 255-nroots) over conventional-basis bytes. msgs: [n, k] uint8."""
-    fcr = 112 if nroots == 32 else 120
-    g = rs_generator(nroots, fcr, 11)[1:]  # drop leading 1
+def _rs_lfsr(msgs: np.ndarray, g: np.ndarray) -> np.ndarray:
+    """Parity bytes of the systematic encoder's feedback register, one message byte at a time. msgs: [n, k] uint8."""
     n, k = msgs.shape
-    par = np.zeros((n, nroots), dtype=np.int32)
+    par = np.zeros((n, len(g)), dtype=np.int32)
     for i in range(k):
         fb = msgs[:, i].astype(np.int32) ^ par[:, 0]
         par = np.concatenate([par[:, 1:], np.zeros((n, 1), dtype=np.int32)], axis=1)
         par ^= gf_mul(fb[:, None], g[None, :])
-    return np.concatenate([msgs, par.astype(np.uint8)], axis=1)
+    return par.astype(np.uint8)
+
+
+def rs_encode(msgs: np.ndarray, nroots=32) -> np.ndarray:
+    """Systematic RS(255, 255-nroots) over conventional-basis bytes. msgs: [n, k] uint8.
+    The parity is GF(256)-linear in the message, so it is the XOR over positions i of v_i * parity(unit message at i): one table
+    row per (position, byte value), looked up eight parity bytes at a time -- the same bytes as the register, at bench sizes in seconds."""
+    fcr = 112 if nroots == 32 else 120
+    g = rs_generator(nroots, fcr, 11)[1:]  # drop leading 1
+    n, k = msgs.shape
+    if n < 4096 or nroots % 8:
+        return np.concatenate([msgs, _rs_lfsr(msgs, g)], axis=1)
+    unit = _rs_lfsr(np.eye(k, dtype=np.uint8), g).astype(np.int32)  # [k, nroots]: parity of the unit message at each position
+    tab = gf_mul(np.arange(256, dtype=np.int32)[None, :, None], unit[:, None, :]).astype(np.uint8)  # [k, 256, nroots]
+    tab = np.ascontiguousarray(tab).view(np.uint64)  # [k, 256, nroots / 8]
+    par = np.empty((n, nroots // 8), dtype=np.uint64)
+    for a in range(0, n, 1 << 14):  # in row blocks that stay in cache
+        m = msgs[a:a + (1 << 14)]
+        p = tab[0][m[:, 0]]
+        for i in range(1, k):
+            p ^= tab[i][m[:, i]]
+        par[a:a + len(m)] = p
+    return np.concatenate([msgs, par.view(np.uint8)], axis=1)
 
 
 def ccsds_pn_table() -> np.ndarray:
@@ -151,13 +171,16 @@ def nrzm_encode(bits: np.ndarray) -> np.ndarray:
     return (np.cumsum(bits.astype(np.int64)) & 1).astype(np.uint8)
 
 
-def conv_encode(bits: np.ndarray, circular: bool = False) -> np.ndarray:
-    """k=7 r=1/2, polys {79,109}; returns interleaved coded bits c0[0],c1[0],c0[1],..."""
-    b = bits.astype(np.uint8)
-    if circular:
-        ext = np.concatenate([b[-6:], b])
+def conv_encode(bits, circular: bool = False):
+    """k=7 r=1/2, polys {79,109}; returns interleaved coded bits c0[0],c1[0],c0[1],... (numpy in, numpy out; a torch tensor in: a
+    tensor on its device out)"""
+    if isinstance(bits, np.ndarray):
+        b = bits.astype(np.uint8)
+        ext = np.concatenate([b[-6:] if circular else np.zeros(6, dtype=np.uint8), b])
     else:
-        ext = np.concatenate([np.zeros(6, dtype=np.uint8), b])
+        import torch
+        b = bits.to(torch.uint8)
+        ext = torch.cat([b[-6:] if circular else torch.zeros(6, dtype=torch.uint8, device=b.device), b])
     n = len(b)
 
     def tap(t):  # bit delayed by t
@@ -165,22 +188,18 @@ def conv_encode(bits: np.ndarray, circular: bool = False) -> np.ndarray:
 
     c0 = tap(0) ^ tap(1) ^ tap(2) ^ tap(3) ^ tap(6)  # 79  = 0b1001111
     c1 = tap(0) ^ tap(2) ^ tap(3) ^ tap(5) ^ tap(6)  # 109 = 0b1101101
+    if not isinstance(bits, np.ndarray):
+        return torch.stack([c0, c1], 1).reshape(-1)
     out = np.empty(2 * n, dtype=np.uint8)
     out[0::2] = c0
     out[1::2] = c1
     return out
 
 
-def puncture_metop(coded: np.ndarray) -> np.ndarray:
-    """Mother-code bits m0..m5 per 3 info bits -> QPSK symbols A=(m0,m1), B=(m4,m3)."""
+def puncture_metop(coded):
+    """Mother-code bits m0..m5 per 3 info bits -> QPSK symbols A=(m0,m1), B=(m4,m3). numpy array or torch tensor."""
     n6 = len(coded) // 6
-    m = coded[:n6 * 6].reshape(n6, 6)
-    out = np.empty((n6, 4), dtype=np.uint8)
-    out[:, 0] = m[:, 0]
-    out[:, 1] = m[:, 1]
-    out[:, 2] = m[:, 4]
-    out[:, 3] = m[:, 3]
-    return out.reshape(-1)
+    return coded[:n6 * 6].reshape(n6, 6)[:, [0, 1, 4, 3]].reshape(-1)
 
 
 def fy3_diff_encode(dibits: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
@@ -577,28 +596,48 @@ class Recording:
             f += i1 - i0
         return np.concatenate(out, axis=0) if out else np.zeros((0, 4 + 255 * self.spec.rs_i), dtype=np.uint8)
 
-    def symbols(self, g0, g1):
-        """Symbols of frame groups [g0, g1) (group = self.group frames); first symbol has absolute index g0 * syms_per_group."""
+    def symbols(self, g0, g1, device=None):
+        """Symbols of frame groups [g0, g1) (group = self.group frames); first symbol has absolute index g0 * syms_per_group.
+        device=None: numpy complex64; else the same symbols as a torch.complex64 tensor on `device`, coded and mapped there from the CADU bytes
+        (at bench sizes a gigabit of bits: seconds of host time and gigabytes of copies otherwise)."""
         G = self.group
         fr = self.frames(g0 * G - 1, g1 * G)  # one frame early: convolutional encoder state
-        bits = np.unpackbits(fr.reshape(-1))
         fb = fr.shape[1] * 8
+        if device is None:
+            bits = np.unpackbits(fr.reshape(-1))
+        else:
+            import torch
+            d = torch.from_numpy(fr.reshape(-1)).to(device)
+            bits = ((d[:, None] >> torch.arange(7, -1, -1, dtype=torch.uint8, device=device)) & 1).reshape(-1)  # MSB first, as np.unpackbits
+            del d
         if self.spec.nrzm:
             # level just before the first bit: 0 at every block boundary; backwards from the next boundary otherwise
             first = (g0 * G - 1) % (self.P * self.blocks)
             to_boundary = (self.P - first % self.P) % self.P  # frames from `first` to the next block boundary
-            lvl = int(bits[: to_boundary * fb].sum()) & 1 if to_boundary * fb <= len(bits) else None
-            if lvl is None:
+            if to_boundary > len(fr):
                 raise ValueError("slice does not reach a block boundary: cannot anchor the NRZ-M level")
-            bits = ((np.cumsum(bits.astype(np.int64)) + lvl) & 1).astype(np.uint8)
+            lvl = int(np.unpackbits(fr[:to_boundary].reshape(-1)).sum()) & 1
+            if device is None:
+                bits = ((np.cumsum(bits.astype(np.int64)) + lvl) & 1).astype(np.uint8)
+            else:
+                bits = ((torch.cumsum(bits, 0, dtype=torch.int64) + lvl) & 1).to(torch.uint8)
         coded = conv_encode(bits)
+        del bits
         coded = coded[2 * fb:]  # drop the lead-in frame (its last 6 bits set the encoder state)
         if self.spec.conv == "3/4-metop":
             coded = puncture_metop(coded)
-        lv = coded.astype(np.float32) * 2.0 - 1.0
+        # bit -> level, one pass over gigabytes of bits: BPSK (+-1, 0), QPSK's interleaved bit pairs straight into (re, im) of +-1 / sqrt(2)
         if self.spec.constellation == "bpsk":
-            return lv.astype(np.complex64)
-        return ((lv[0::2] + 1j * lv[1::2]) / np.float32(math.sqrt(2.0))).astype(np.complex64)
+            lv = np.array([-1.0, 0.0, 1.0, 0.0], dtype=np.float32)
+        else:
+            coded = coded[: len(coded) // 2 * 2]
+            lv = np.array([-1.0, 1.0], dtype=np.float32) / np.float32(math.sqrt(2.0))
+        if device is None:
+            return lv.view(np.complex64)[coded] if len(lv) == 4 else lv[coded].view(np.complex64)
+        if len(lv) == 4:
+            re = torch.where(coded.bool(), float(lv[2]), float(lv[0]))
+            return torch.complex(re, torch.zeros_like(re))
+        return torch.where(coded.bool(), float(lv[1]), float(lv[0])).view(torch.complex64)
 
     # ---- samples
     def _bank(self):
@@ -620,7 +659,7 @@ class Recording:
         k_hi = ((b - 1) * self.down) // self.up + span + 1
         g0 = k_lo // spg
         g1 = k_hi // spg + 1
-        sy = self.symbols(g0, g1)
+        sy = self.symbols(g0, g1, device=device)
         ks = g0 * spg  # absolute index of sy[0]
         H = self._bank()
         ntap = 2 * span
@@ -662,8 +701,9 @@ class Recording:
                 out[m0 - a:m1 - a] = ((yr + r * np.cos(t)) * np.float32(self.spec.amplitude)) + 1j * ((yi + r * np.sin(t)) * np.float32(self.spec.amplitude))
             return out
         import torch
-        d_ar = torch.from_numpy(np.ascontiguousarray(sy.real)).to(device)
-        d_ai = None if is_real else torch.from_numpy(np.ascontiguousarray(sy.imag)).to(device)
+        d_ar = sy.real.contiguous()
+        d_ai = None if is_real else sy.imag.contiguous()
+        del sy
         d_H = torch.from_numpy(H.astype(np.float32)).to(device)
         out = torch.empty(b - a, dtype=torch.complex64, device=device)
         for m0 in range(a, b, chunk):

@@ -19,6 +19,7 @@ Fixtures (np.savez_compressed):
   s2_bb_to_soft.npz  DVB-S2 S2BBToSoft (PLS decode, PL descrambling, table demapping, de-interleaver) on stored short QPSK PLFRAMEs
   ndsp_psk_*.npz  ndsp PSKDemodHierBlock (RRC -> AGC -> M&M -> Costas), stored cs16 samples -> complex symbols
   taps.npz        RRC / M&M interpolator bank / rational-resampler bank
+  demod_dc_block.npz  PSKDemodModule chain with dc_block=1 in front of the rational resampler: cf32 IQ (stored) -> int8 soft + float symbols
 """
 import hashlib
 import os
@@ -177,6 +178,14 @@ def main():
     bank, ir, dr = ref.resamp_bank(2700000, 3000000)
     out["taps"] = dict(rrc_goes=ref.rrc_taps(2.7e6, 927000, 0.5, 31), rrc_metop=ref.rrc_taps(6e6, 2333333, 0.5, 31), mm=ref.mm_bank(128, 8),
                        resamp=bank, resamp_ratio=np.array([ir, dr], dtype=np.int32))
+
+    # ---- PSKDemodModule with dc_block=1 in front of the rational resampler (tests/test_zy_demod_additions_gpu.py::test_dc_block_in_front_of_the_resampler):
+    # the restatement does not implement that combination, so the reference's output is stored with its input
+    rng = np.random.default_rng(77)
+    n = 60000
+    x = ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.3 + (0.05 - 0.02j)).astype(np.complex64)
+    r = ref.psk_demod(pyref.demod_cfg(constellation=pyref.QPSK, samplerate=19153000.0, symbolrate=3.5e6, rrc_alpha=0.5, rrc_taps=21, pll_bw=0.006, dc_block=1), x)
+    out["demod_dc_block"] = {"x": x, "soft": r["soft"], "syms": r["syms"], "final_sps": np.float32(r["final_sps"])}
 
     # `make_golden.py name ...` rewrites only the named fixtures (and their INDEX lines): an .npz is a zip with time stamps, so
     # rewriting an unchanged fixture would still change its bytes

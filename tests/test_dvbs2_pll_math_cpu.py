@@ -38,9 +38,9 @@ def test_kernel_atan2f_equals_libm_on_1e7_arguments(capi):
     assert bad == 0
 
 
-def test_standalone_c_check_builds_and_passes_on_a_sample():
+def test_standalone_c_check_builds_and_passes_on_a_sample(tmp_path):
     """tools/check_atan2f.c compiles and reports bad=0 (its full 6e7-argument run takes ~10 s: run here as it is)."""
-    exe = "/tmp/sdhip_check_atan2f"
+    exe = str(tmp_path / "check_atan2f")
     subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-o", exe, os.path.join(ROOT, "tools", "check_atan2f.c"), "-lm"])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300).stdout
     assert "bad=0" in out, out

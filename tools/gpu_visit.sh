@@ -5,7 +5,7 @@
 #   suite            pytest -m gpu (whole suite), tail -> pytest_gpu.txt          (SDHIP_FINAL=1 in the environment: the closing run)
 #   tests:<expr>     pytest -m gpu -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   driver           python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's own command) -> bench_line.json + bench_detail.json
+#   driver           python bench.py --full --gpus 1 --steps 20 --warmup 5 (the driver's command, with every leg) -> bench_line.json + bench_detail.json
 #   quick:<wl>       bench.py on one workload, parity over 400 M samples, no other rows (~1.5 min) -> quick_<wl>.json (the full object); extra SDHIP_* env applies
 #   ab:<wl>:<VAR=v,VAR=v>   the same under the given environment -> ab_<wl>_<VAR=v,..>.json
 #   stats:<wl>       rocprofv3 --kernel-trace --stats of 3 timed steps -> <wl>_kernel_stats.csv
@@ -18,14 +18,14 @@
 TAG=${1:?tag}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-QUICK="--others 0 --next-rows 0 --exact-samples 0 --streamed-samples 0 --parity-samples 400000000 --steps 6 --warmup 2"
+QUICK="--full --others 0 --next-rows 0 --exact-samples 0 --streamed-samples 0 --parity-samples 400000000 --steps 6 --warmup 2"
 for ST in "$@"; do
   echo "=== $ST"
   case $ST in
     suite)   python -m pytest tests -m gpu -x -q 2>&1 | tail -8 | tee $OUT/pytest_gpu.txt ;;
     tests:*) python -m pytest tests -m gpu -x -q -k "${ST#tests:}" 2>&1 | tail -8 | tee -a $OUT/pytest_some.txt ;;
     smoke)   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee $OUT/smoke.txt ;;
-    driver)  python bench.py --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_detail.json > $OUT/bench_line.json 2> $OUT/bench.err; echo rc=$?; wc -c $OUT/bench_line.json; cat $OUT/bench_line.json; tail -3 $OUT/bench.err ;;
+    driver)  python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_detail.json > $OUT/bench_line.json 2> $OUT/bench.err; echo rc=$?; wc -c $OUT/bench_line.json; cat $OUT/bench_line.json; tail -3 $OUT/bench.err ;;
     quick:*) WL=${ST#quick:}; python bench.py --workload $WL $QUICK --detail $OUT/quick_$WL.json > $OUT/quick_$WL.line 2> $OUT/quick_$WL.err; echo rc=$?; cat $OUT/quick_$WL.line; tail -3 $OUT/quick_$WL.err ;;
     ab:*)    R=${ST#ab:}; WL=${R%%:*}; ENVS=${R#*:}; ( for kv in ${ENVS//,/ }; do export "$kv"; done; python bench.py --workload $WL $QUICK --detail $OUT/ab_${WL}_$ENVS.json > $OUT/ab_${WL}_$ENVS.line 2> $OUT/ab_${WL}_$ENVS.err; echo rc=$?; cat $OUT/ab_${WL}_$ENVS.line; tail -3 $OUT/ab_${WL}_$ENVS.err ) ;;
     stats:*) WL=${ST#stats:}; CMD="python bench.py --workload $WL --steps 3 --warmup 1 --cpu-samples 0 --others 0 --next-rows 0"
