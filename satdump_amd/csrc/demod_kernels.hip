@@ -6,7 +6,9 @@
 // precision with the same polynomial and reduction, so that a single sequential lane reproduces the
 // reference bit for bit (tests/test_demod_gpu.py, exact mode).
 #include "demod_kernels.h"
+#include <climits>
 #include <optional>
+#include <type_traits>
 
 namespace sdhip
 {
@@ -143,6 +145,15 @@ namespace sdhip
         return sqrtf(x);
 #else
         return __builtin_amdgcn_sqrtf(x); // v_sqrt_f32, 1 ulp
+#endif
+    }
+    // x clipped to [lo, hi] (lo <= hi) in one v_med3_f32: x < lo ? lo : (x > hi ? hi : x) for every x but NaN (the selects pass NaN on, med3 returns lo)
+    __device__ __forceinline__ float sd_clip_med3(float x, float lo, float hi)
+    {
+#ifdef SDHIP_HOST_TWIN
+        return x != x ? lo : x < lo ? lo : (x > hi ? hi : x);
+#else
+        return __builtin_amdgcn_fmed3f(x, lo, hi);
 #endif
     }
 
@@ -2662,6 +2673,57 @@ namespace sdhip
         else
             return mm_iter<FAST, false, RING>(s, p, ring, bank, omega_gain, mu_gain);
     }
+    // mm_iter<FAST, false, RING> on a delay line held in named pairs instead of an MmState (k_mm's fast paths, UNR): mm_iter never reads its oldest
+    // pair after the rotation, so the new symbol goes INTO it (p_new / c_new: p_2T / c_2T before the step) while the two before it serve as p_1T / p_2T
+    // -- three steps in a row pass the roles round three registers with no copies. Same statements in the same order; the detector takes its operands
+    // as the (re, im) pairs they are: (p_0T - p_2T) * c_1T and (c_0T - c_2T) * p_1T, one v_pk_add_f32 and one v_pk_mul_f32 each, and x - y * (-z) is
+    // x + y * z bit for bit. The sample index runs as rel = inc - to in 32 bits (to = end of the feed; roff = (to - 7) & (RING - 1) puts the window
+    // where mm_iter finds it); lo = the rel of inc = 0, where mm_iter clamps inc.
+    template <bool FAST, int RING>
+    __device__ __forceinline__ v2f mm_sym(float &mu, float &omega, int &rel, v2f &p_new, v2f &c_new, const v2f p_1, const v2f p_2, const v2f c_1, const v2f c_2,
+                                          const MmParams &p, const cf32 *ring, const int roff, const int lo, const float *bank, const float omega_gain,
+                                          const float mu_gain)
+    {
+        int imu = (int)rintf(mu * 128.0f);
+        if (imu < 0)
+            imu = 0;
+        if (imu >= 128)
+            imu = 127;
+        const float4 t0 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE);
+        const float4 t1 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE + 4);
+        const float t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+        const int base = (rel + roff) & (RING - 1);
+        v2f acc{0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+        {
+            const cf32 v = ring[(base + k) * MM_RING_STRIDE];
+            if constexpr (FAST)
+                acc = __builtin_elementwise_fma(v2f{v.re, v.im}, v2f{t[k], t[k]}, acc);
+            else
+            {
+                const v2f prod = v2f{v.re, v.im} * v2f{t[k], t[k]};
+                acc = acc + prod;
+            }
+        }
+        p_new = acc;
+        c_new = v2f{acc.x > 0.0f ? 1.0f : 0.0f, acc.y > 0.0f ? 1.0f : 0.0f};
+        const v2f a = (acc - p_2) * c_1, b = (c_new - c_2) * p_1;
+        float a_re = a.x + a.y;
+#ifndef SDHIP_HOST_TWIN
+        asm("" : "+v"(a_re)); // (keeps the two sums scalar: packed, their operands cost three moves)
+#endif
+        // the clips as v_med3_f32: mm_iter's selects for every pe but NaN (which mm_iter passes on, stalling its lane's timing for good)
+        const float pe = sd_clip_med3(a_re - (b.x + b.y), -1.0f, 1.0f);
+        omega = omega + omega_gain * pe;
+        const float d = sd_clip_med3(omega - p.omega_mid, -p.omega_limit, p.omega_limit);
+        omega = p.omega_mid + d;
+        mu = (mu + omega) + mu_gain * pe;
+        const float fl = floorf(mu);
+        rel = max(rel + (int)fl, lo);
+        mu = mu - fl;
+        return acc;
+    }
 
     // CKPT: whenever the block ending at a multiple of MM_CK_SAMPLES samples into its chunk has been fed, a lane leaves a
     // checkpoint {mu, omega, inc, symbols so far}. A re-run lane (exact start state) compares itself with the checkpoint at the
@@ -2691,12 +2753,15 @@ namespace sdhip
     }
     // FEED: samples moved into the ring per pass of the symbol loop (see block_body / feed_body below): 8, or 16 for the chunk-parallel M&M instances the
     // timed step runs (SDHIP_MM_FEED=8 for A/B; the cooperative loads, Gardner, LIN and the tap keep 8)
-    template <bool CKPT, bool SPLIT, bool Q8 = false, bool FAST = false, bool GARD = false, bool TAP = false, bool LIN = false, int FEED = 8>
+    // UNR: the wave-uniform fast paths run their symbols three at a time through mm_sym, without the per-symbol state rotation (the 16-sample feeds'
+    // M&M instances; SDHIP_MM_LOOP=0 keeps the one-symbol loop for A/B)
+    template <bool CKPT, bool SPLIT, bool Q8 = false, bool FAST = false, bool GARD = false, bool TAP = false, bool LIN = false, int FEED = 8, bool UNR = false>
     __global__ __launch_bounds__(64) void k_mm(const cf32 *x, cf32 *sym, int *counts, ChunkGeom g, MmParams p, const MmState *start0, MmState *spec,
                                                MmState *endst, MmCert *spec_c, MmCert *end_c, const int *redo, int nredo, MmCkpt *ck, int ck_per_chunk,
                                                float ck_tol, int coop_nb)
     {
         static_assert(FEED == 8 || (!GARD && !LIN && !SPLIT), "longer feeds: the M&M instances only");
+        static_assert(!UNR || (FEED > 8 && !TAP), "the unrolled fast paths: the M&M instances with longer feeds");
         constexpr int RING = GARD ? MM_RING : mm_ring_mm<FEED>();
         __shared__ cf32 rings[(RING + MM_MIRROR) * MM_RING_STRIDE];
         __shared__ __attribute__((aligned(16))) float bank[128 * MM_ARM_STRIDE];
@@ -2781,7 +2846,8 @@ namespace sdhip
                     o8[q_last - 7 + j] = (short)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xffffu));
             qn = 0;
         };
-        auto put = [&](int at, const cf32 v) {
+        // (push: put without the note of the last index, for a loop that sets q_last once at its end)
+        auto push = [&](int at, const cf32 v) {
             if constexpr (Q8)
             {
                 const float sc = p.q8_bpsk ? 50.0f : 100.0f;
@@ -2791,7 +2857,6 @@ namespace sdhip
                 q2 = (q2 >> 16) | (q3 << 16);
                 q3 = (q3 >> 16) | (cur << 16);
                 qn++;
-                q_last = at;
                 if (qn == 8)
                 { // (a lane's first index is 0, so `at - 7` is a multiple of eight and the store aligned; it would be correct, only slower, from any other start)
                     *reinterpret_cast<uint4 *>(o8 + at - 7) = uint4{q0, q1, q2, q3};
@@ -2800,6 +2865,11 @@ namespace sdhip
             }
             else
                 o[at] = v;
+        };
+        auto put = [&](int at, const cf32 v) {
+            push(at, v);
+            if constexpr (Q8)
+                q_last = at;
         };
         int phase = warm ? 0 : 1, cnt = 0, nx = 0, wsym = 0;
         bool done = false, merged = false;
@@ -2826,6 +2896,61 @@ namespace sdhip
                         }
                     }
                 }
+        };
+        // UNR: the fast paths' symbol loop, every symbol in front of `to` for a lane inside its chunk (CH) or in its warm-up: mm_sym three times per pass,
+        // the delay line in the pairs x* / y* (p_*, c_*), each step's new symbol in the oldest pair; a lane that reaches `to` after the first or second
+        // step of a pass skips the rest and leaves the loop at its end. The MmState order is put back once per feed from the number of symbols run --
+        // spec, endst, the checkpoints and the per-symbol path see the state mm_iter leaves. Same steps, same order, same results.
+        const auto run3 = [&](const long long to, auto chunk) __attribute__((always_inline)) {
+                constexpr bool CH = decltype(chunk)::value;
+                int rel = (int)(s.inc - to); // a window lies inside the ring: |inc - to| < 2 RING
+                if (rel >= 0)
+                    return;
+                const int roff = (int)((to - 7) & (RING - 1)), lo = (int)(to > 0x7fffffffll ? (long long)INT_MIN : -to);
+                const int n0 = CH ? cnt : wsym;
+                float mu = s.mu, om = s.omega;
+                v2f x0{s.p_0T.re, s.p_0T.im}, x1{s.p_1T.re, s.p_1T.im}, x2{s.p_2T.re, s.p_2T.im};
+                v2f y0{s.c_0T.re, s.c_0T.im}, y1{s.c_1T.re, s.c_1T.im}, y2{s.c_2T.re, s.c_2T.im};
+                const auto step = [&](v2f &pn, v2f &cn, const v2f p1, const v2f p2, const v2f c1, const v2f c2) __attribute__((always_inline)) {
+                        if constexpr (CH)
+                        {
+                            const v2f v = mm_sym<FAST, RING>(mu, om, rel, pn, cn, p1, p2, c1, c2, p, f.ring, roff, lo, bank, p.omega_gain, p.mu_gain);
+                            push(cnt, cf32{v.x, v.y});
+                            cnt++;
+                        }
+                        else
+                        {
+                            const bool fast = wsym < p.fast_syms;
+                            wsym++;
+                            (void)mm_sym<FAST, RING>(mu, om, rel, pn, cn, p1, p2, c1, c2, p, f.ring, roff, lo, bank, fast ? 0.0f : p.omega_gain,
+                                                     fast ? p.mu_gain * p.fast_mult : p.mu_gain);
+                        }
+                };
+                do
+                {
+                    step(x2, y2, x0, x1, y0, y1);
+                    if (rel < 0)
+                    {
+                        step(x1, y1, x2, x0, y2, y0);
+                        if (rel < 0)
+                            step(x0, y0, x1, x2, y1, y2);
+                    }
+                } while (rel < 0);
+                if constexpr (CH && Q8)
+                    q_last = cnt - 1;
+                // after 3j + 1 symbols the newest pair is x2 (then x0, x1), after 3j + 2 it is x1 (then x2, x0)
+                const int ph = ((CH ? cnt : wsym) - n0) % 3;
+                const v2f q0 = ph == 1 ? x2 : ph == 2 ? x1 : x0, q1 = ph == 1 ? x0 : ph == 2 ? x2 : x1, q2 = ph == 1 ? x1 : ph == 2 ? x0 : x2;
+                const v2f r0 = ph == 1 ? y2 : ph == 2 ? y1 : y0, r1 = ph == 1 ? y0 : ph == 2 ? y2 : y1, r2 = ph == 1 ? y1 : ph == 2 ? y0 : y2;
+                s.p_0T = cf32{q0.x, q0.y};
+                s.p_1T = cf32{q1.x, q1.y};
+                s.p_2T = cf32{q2.x, q2.y};
+                s.c_0T = cf32{r0.x, r0.y};
+                s.c_1T = cf32{r1.x, r1.y};
+                s.c_2T = cf32{r2.x, r2.y};
+                s.mu = mu;
+                s.omega = om;
+                s.inc = to + rel;
         };
         // every symbol whose window ends in front of sample `to` (<= f.next)
         const auto run_syms = [&](const long long to) __attribute__((always_inline)) {
@@ -2895,6 +3020,11 @@ namespace sdhip
                     const unsigned long long act = __ballot(1);
                     if (__ballot(!done && phase == 1 && to <= e && cnt + FEED < p.cap) == act) // (!done: a re-run lane that merged at a checkpoint stays out)
                     {
+                        if constexpr (UNR)
+                        {
+                            run3(to, std::true_type{});
+                            return;
+                        }
                         while (s.inc < to)
                         {
                             const cf32 v = clock_iter<GARD, FAST, TAP, RING, LIN>(s, p, f.ring, bank, p.omega_gain, p.mu_gain);
@@ -2905,6 +3035,11 @@ namespace sdhip
                     }
                     if (__ballot(!done && phase == 0 && to <= b) == act)
                     {
+                        if constexpr (UNR)
+                        {
+                            run3(to, std::false_type{});
+                            return;
+                        }
                         while (s.inc < to)
                         {
                             const bool fast = wsym < p.fast_syms;
@@ -3105,18 +3240,33 @@ namespace sdhip
         const int feed = coop_nb > 0 ? 8 : feed_env ? atoi(feed_env) : 16;
         if (feed != 8 && feed != 16)
             throw HipError("SDHIP_MM_FEED: 8 or 16");
-        if (ck && p.q8 && p.fast && feed == 16)
+        // their fast paths run three symbols per pass without the state rotation (SDHIP_MM_LOOP=0: one symbol per pass, as before; same results bit for bit)
+        // (mm_sym clips the rate with v_med3_f32: the selects' value for a limit >= 0 -- a negative relative limit keeps the one-symbol loop)
+        const char *loop_env = getenv("SDHIP_MM_LOOP");
+        const int loop_sw = loop_env ? atoi(loop_env) : 1;
+        if (loop_sw != 0 && loop_sw != 1)
+            throw HipError("SDHIP_MM_LOOP: 0 or 1");
+        const bool unr = loop_sw == 1 && p.omega_limit >= 0.0f;
+        if (ck && p.q8 && p.fast && feed == 16 && unr)
+            go(k_mm<true, false, true, true, false, false, false, 16, true>, ck, ck_per_chunk, ck_tol);
+        else if (ck && p.q8 && p.fast && feed == 16)
             go(k_mm<true, false, true, true, false, false, false, 16>, ck, ck_per_chunk, ck_tol);
         else if (ck && p.q8 && p.fast)
             go(k_mm<true, false, true, true>, ck, ck_per_chunk, ck_tol);
+        else if (ck && p.q8 && feed == 16 && unr)
+            go(k_mm<true, false, true, false, false, false, false, 16, true>, ck, ck_per_chunk, ck_tol);
         else if (ck && p.q8 && feed == 16)
             go(k_mm<true, false, true, false, false, false, false, 16>, ck, ck_per_chunk, ck_tol);
         else if (ck && p.q8)
             go(k_mm<true, false, true>, ck, ck_per_chunk, ck_tol);
+        else if (ck && p.fast && feed == 16 && unr)
+            go(k_mm<true, false, false, true, false, false, false, 16, true>, ck, ck_per_chunk, ck_tol);
         else if (ck && p.fast && feed == 16)
             go(k_mm<true, false, false, true, false, false, false, 16>, ck, ck_per_chunk, ck_tol);
         else if (ck && p.fast)
             go(k_mm<true, false, false, true>, ck, ck_per_chunk, ck_tol);
+        else if (ck && feed == 16 && unr)
+            go(k_mm<true, false, false, false, false, false, false, 16, true>, ck, ck_per_chunk, ck_tol);
         else if (ck && feed == 16)
             go(k_mm<true, false, false, false, false, false, false, 16>, ck, ck_per_chunk, ck_tol);
         else if (ck)
