@@ -2204,7 +2204,7 @@ namespace sdhip
                 g = make_geom(n, L, (int)Wn);
                 const double omin = (double)mm_p.omega_mid - (double)mm_p.omega_limit;
                 const long long span0 = std::min<long long>(n, (long long)L + Wn);
-                mm_p.cap = ((int)(span0 / std::max(0.5, omin - 0.01)) + 16 + 7) & ~7; // whole groups of eight: int8 rows start on 16 bytes (k_mm<.., Q8>'s group stores)
+                mm_p.cap = ((int)(span0 / std::max(0.5, omin - 0.01)) + 16 + 7) & ~7; // whole groups of eight: int8 rows start on 16 bytes (k_mm<MM_Q8 | ..>'s group stores)
                 mm_p.cg = cg;
                 mm_p.rot = mm_rot;
                 symbuf.reserve((size_t)g.K * mm_p.cap);
@@ -2219,7 +2219,7 @@ namespace sdhip
                 d_seg.reserve(2 * (size_t)g.K);
                 ck_per_chunk = L / MM_CK_SAMPLES + 2;
                 if (use_ckpt || env_int("SDHIP_MM_CKPT", 0))
-                { // checkpoints for the early exit of re-run lanes, k_mm<true>
+                { // checkpoints for the early exit of re-run lanes, k_mm<MM_CKPT | ..>
                     d_mm_ck.reserve((size_t)g.K * ck_per_chunk);
                     ckp = d_mm_ck.p;
                 }

@@ -12,6 +12,12 @@
 
 namespace sdhip
 {
+    // an integer switch of the launchers below, read at every launch (tests and tools/ab_demod.py switch them inside one process); like DemodEngine::env_int
+    static int env_int(const char *name, int dflt)
+    {
+        const char *v = getenv(name);
+        return (v && *v) ? atoi(v) : dflt;
+    }
     // =============================================================================================
     // glibc 2.35 sinf / cosf (sysdeps/ieee754/flt-32/s_sincosf.h, x86-64 FMA build), |x| < 120
     // =============================================================================================
@@ -1998,7 +2004,7 @@ namespace sdhip
             // ck_len is also the spacing at which the lane looks for the chunk start (spec snapshot): always a power of two >= 32
             // cooperative access of the wave's 64 streams (see Coop): every stage range a whole number of 128-byte bursts (chunk length, warm-ups, estimator
             // window: multiples of 16 samples), every chunk from 1 on with its whole warm-up inside the call, and at least one full wave of ordinary chunks
-            const bool coop_env = !(getenv("SDHIP_COOP") && atoi(getenv("SDHIP_COOP")) == 0); // (read per launch: tests and tools/ab_demod.py switch it in one process)
+            const bool coop_env = env_int("SDHIP_COOP", 1) != 0; // (read per launch: tests and tools/ab_demod.py switch it in one process)
             int coop_nb = 0;
             if (coop_env && !redo && g.L % 16 == 0 && g.W % 16 == 0 && p.w_agc % 16 == 0 && p.cos.est_len % 16 == 0 && (long long)g.L > (long long)p.w_agc && g.K >= 66)
                 coop_nb = (g.K - 2) / 64; // chunks 1 .. 64 coop_nb; chunk 0 and the rest (the last chunk among them) on the per-lane path
@@ -2382,12 +2388,7 @@ namespace sdhip
                                    // + 4 KB of interpolator arms per wave lets a CU hold eight blocks -- two waves on every SIMD (it was six: one and a half)
     // The symbol loop runs once per FEED samples (k_mm's FEED: 8 or 16). A feed moves FEED / 8 blocks into the ring first, so a window [inc-7, inc] with
     // inc >= the feed's first sample reaches FEED + 7 samples back from the newest: the ring holds at least FEED + 8 slots (a power of two for the slot mask)
-    template <int FEED>
-    constexpr int mm_ring_mm()
-    {
-        static_assert(FEED == 8 || FEED == 16 || FEED == 32, "k_mm feeds are whole blocks of the 4-deep queue");
-        return FEED == 8 ? MM_RING_MM : FEED == 16 ? 32 : 64;
-    }
+    constexpr int mm_ring_mm(const int feed) { return feed == 8 ? MM_RING_MM : 32; }
     // ring[slot][lane]: slot-major, so lane l of a 32-lane LDS access group always owns 8-byte bank pair l whatever slot it
     // addresses -- the lanes' windows sit at unrelated ring positions, and a lane-major layout made them collide at random
     // (SQ: bank-conflict cycles were twice the active LDS cycles)
@@ -2483,10 +2484,10 @@ namespace sdhip
         }
     }
 
-    // one iteration of MMClockRecoveryBlock<complex_t>::work's loop body, clock_recovery_mm.cpp:54-120; the window
-    // [inc-7, inc] must be in the ring
-    // the body of ndsp::MMClockRecoveryFastBlock<complex_t>::work's loop behind its delay-line shift (dsp/clock_recovery/clock_recovery_mm_fast.cpp:108-150), x0 / x1 = the
-    // block's buffer[inc] / buffer[inc + 1] = samples inc - 7 / inc - 6 of the stream
+    // LIN: ndsp::MMClockRecoveryFastBlock<complex_t>::work's loop body instead (dsp/clock_recovery/clock_recovery_mm_fast.cpp:96-150): the symbol is the linear
+    // interpolation buffer[inc] * (1.0 - mu) + buffer[inc + 1] * mu -- samples inc - 7 and inc - 6 of the stream, the block's buffer holding ntaps - 1 = 7 samples of
+    // history in front; (1.0 - mu) taken in double and rounded to the float complex_t::operator*(const float &) takes -- and the rate term moves on every fifth symbol
+    // (this function: the body of that loop behind its delay-line shift, :108-150, x0 / x1 = the block's buffer[inc] / buffer[inc + 1])
     __device__ __forceinline__ cf32 mmfast_core(MmState &s, const MmParams &p, const cf32 x0, const cf32 x1, const float omega_gain, const float mu_gain)
     {
         const float w0 = (float)(1.0 - (double)s.mu);
@@ -2519,9 +2520,44 @@ namespace sdhip
         return out;
     }
 
-    // LIN: ndsp::MMClockRecoveryFastBlock<complex_t>::work's loop body instead (dsp/clock_recovery/clock_recovery_mm_fast.cpp:96-150): the symbol is the linear
-    // interpolation buffer[inc] * (1.0 - mu) + buffer[inc + 1] * mu -- samples inc - 7 and inc - 6 of the stream, the block's buffer holding ntaps - 1 = 7 samples of
-    // history in front; (1.0 - mu) taken in double and rounded to the float complex_t::operator*(const float &) takes -- and the rate term moves on every fifth symbol
+    // the polyphase interpolator: arm imu of the bank (two 16-byte LDS loads) times the 8-sample window that starts at ring slot `base` (mirror region: 8
+    // consecutive slots). (re, im) of a sample as one packed pair: v_pk_mul_f32 / v_pk_add_f32, each half rounded like the scalar operation; FAST: fused, the
+    // chunk-parallel mode's arithmetic (see sd_sincosf_fast)
+    template <bool FAST>
+    __device__ __forceinline__ v2f mm_interp(const cf32 *ring, const int base, const float *bank, const int imu)
+    {
+        const float4 t0 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE);
+        const float4 t1 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE + 4);
+        const float t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+        v2f acc{0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+        {
+            const cf32 v = ring[(base + k) * MM_RING_STRIDE];
+            if constexpr (FAST)
+                acc = __builtin_elementwise_fma(v2f{v.re, v.im}, v2f{t[k], t[k]}, acc);
+            else
+            {
+                const v2f prod = v2f{v.re, v.im} * v2f{t[k], t[k]};
+                acc = acc + prod;
+            }
+        }
+        return acc;
+    }
+    // warm-up gear shift: the first fast_syms symbols of a warm-up run with the timing gain raised and the rate term frozen (pull-in in ~1/fast_mult of the
+    // time), the rest with the loop's own gains so that the trajectory settles onto the sequential one; only speculation -- the boundary certificate decides.
+    // mm_gear_fast counts the symbol in wsym and says whether it runs in the fast gear; warm = false (a symbol of the chunk or its look-ahead): never
+    __device__ __forceinline__ bool mm_gear_fast(const MmParams &p, int &wsym, const bool warm = true)
+    {
+        const bool fast = warm && wsym < p.fast_syms;
+        wsym++;
+        return fast;
+    }
+    __device__ __forceinline__ float mm_gear_omega(const MmParams &p, const bool fast) { return fast ? 0.0f : p.omega_gain; }
+    __device__ __forceinline__ float mm_gear_mu(const MmParams &p, const bool fast) { return fast ? p.mu_gain * p.fast_mult : p.mu_gain; }
+
+    // one iteration of MMClockRecoveryBlock<complex_t>::work's loop body, clock_recovery_mm.cpp:54-120; the window
+    // [inc-7, inc] must be in the ring (LIN: mmfast_core's loop body on the same window)
     template <bool FAST = false, bool TAP = false, int RING = MM_RING, bool LIN = false>
     __device__ __forceinline__ cf32 mm_iter(MmState &s, const MmParams &p, const cf32 *ring, const float *bank, const float omega_gain, const float mu_gain,
                                             long long *arm_pos = nullptr)
@@ -2542,24 +2578,7 @@ namespace sdhip
             imu = 127;
         if constexpr (TAP)
             *arm_pos = s.inc * 128 + imu;
-        const float4 t0 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE);
-        const float4 t1 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE + 4);
-        const float t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-        const int base = (int)((s.inc - 7) & (RING - 1));
-        // (re, im) of a sample as one packed pair: v_pk_mul_f32 / v_pk_add_f32, each half rounded like the scalar operation
-        v2f acc{0.0f, 0.0f};
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-        {
-            const cf32 v = ring[(base + k) * MM_RING_STRIDE];
-            if constexpr (FAST)
-                acc = __builtin_elementwise_fma(v2f{v.re, v.im}, v2f{t[k], t[k]}, acc); // chunk-parallel mode's arithmetic (see sd_sincosf_fast)
-            else
-            {
-                const v2f prod = v2f{v.re, v.im} * v2f{t[k], t[k]};
-                acc = acc + prod;
-            }
-        }
+        const v2f acc = mm_interp<FAST>(ring, (int)((s.inc - 7) & (RING - 1)), bank, imu);
         const float re = acc.x, im = acc.y;
         s.p_0T.re = re;
         s.p_0T.im = im;
@@ -2606,36 +2625,8 @@ namespace sdhip
         imu = imu < 0 ? 0 : (imu >= 128 ? 127 : imu);
         if (offzc > p.back) // cannot happen inside the omega limits the engine admits; keeps a wild state inside the ring
             offzc = p.back;
-        const float4 z0 = *reinterpret_cast<const float4 *>(bank + imuz * MM_ARM_STRIDE), z1 = *reinterpret_cast<const float4 *>(bank + imuz * MM_ARM_STRIDE + 4);
-        const float4 t0 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE), t1 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE + 4);
-        const float tz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
-        const float t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-        const int base = (int)((s.inc - 7) & (MM_RING - 1)), basez = (int)((s.inc - offzc - 7) & (MM_RING - 1));
-        v2f az{0.0f, 0.0f}, as{0.0f, 0.0f};
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-        {
-            const cf32 v = ring[(basez + k) * MM_RING_STRIDE];
-            if constexpr (FAST)
-                az = __builtin_elementwise_fma(v2f{v.re, v.im}, v2f{tz[k], tz[k]}, az);
-            else
-            {
-                const v2f prod = v2f{v.re, v.im} * v2f{tz[k], tz[k]};
-                az = az + prod;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-        {
-            const cf32 v = ring[(base + k) * MM_RING_STRIDE];
-            if constexpr (FAST)
-                as = __builtin_elementwise_fma(v2f{v.re, v.im}, v2f{t[k], t[k]}, as);
-            else
-            {
-                const v2f prod = v2f{v.re, v.im} * v2f{t[k], t[k]};
-                as = as + prod;
-            }
-        }
+        const v2f az = mm_interp<FAST>(ring, (int)((s.inc - offzc - 7) & (MM_RING - 1)), bank, imuz);
+        const v2f as = mm_interp<FAST>(ring, (int)((s.inc - 7) & (MM_RING - 1)), bank, imu);
         const float zr = az.x, zi = az.y, sr = as.x, si = as.y;
         float pe = zr * (s.p_0T.re - sr) + zi * (s.p_0T.im - si);
         if (p.clip_float)
@@ -2689,23 +2680,7 @@ namespace sdhip
             imu = 0;
         if (imu >= 128)
             imu = 127;
-        const float4 t0 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE);
-        const float4 t1 = *reinterpret_cast<const float4 *>(bank + imu * MM_ARM_STRIDE + 4);
-        const float t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-        const int base = (rel + roff) & (RING - 1);
-        v2f acc{0.0f, 0.0f};
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-        {
-            const cf32 v = ring[(base + k) * MM_RING_STRIDE];
-            if constexpr (FAST)
-                acc = __builtin_elementwise_fma(v2f{v.re, v.im}, v2f{t[k], t[k]}, acc);
-            else
-            {
-                const v2f prod = v2f{v.re, v.im} * v2f{t[k], t[k]};
-                acc = acc + prod;
-            }
-        }
+        const v2f acc = mm_interp<FAST>(ring, (rel + roff) & (RING - 1), bank, imu);
         p_new = acc;
         c_new = v2f{acc.x > 0.0f ? 1.0f : 0.0f, acc.y > 0.0f ? 1.0f : 0.0f};
         const v2f a = (acc - p_2) * c_1, b = (c_new - c_2) * p_1;
@@ -2725,6 +2700,32 @@ namespace sdhip
         return acc;
     }
 
+    // quantiser, module_psk_demod.cpp:199-213 + clamp module_demod_base.h:106-113
+    __device__ __forceinline__ signed char sd_clamp8(float x)
+    {
+        if (x < -128.0f)
+            return -127;
+        if (x > 127.0f)
+            return 127;
+        return (signed char)(int)x;
+    }
+    // the same value without branches (the symbol loop of k_mm<MM_Q8 | ..>): inside [-128, 127] the conversion truncates as above, beyond 127 the clamp yields 127,
+    // below -128 the select puts -127 where the clamp left -128
+    __device__ __forceinline__ unsigned sd_clamp8_u(float x)
+    {
+        const int r = (int)fminf(fmaxf(x, -128.0f), 127.0f);
+        return (unsigned)(x < -128.0f ? -127 : r) & 0xffu;
+    }
+    // The variants of k_mm: one flag word V, an OR of (who sets the flag: launch_mm, from the stage's MmParams and the switches named)
+    constexpr unsigned MM_CKPT = 1,     // checkpoints for the early exit of re-run lanes (the engine hands a checkpoint array: chunk-parallel mode unless SDHIP_CKPT=0)
+                       MM_SPLIT = 2,    // the symbol loop as one plain loop per phase (experimental: SDHIP_MM_SPLIT=1, float rows without checkpoints)
+                       MM_Q8 = 4,       // the symbols leave as the modules' int8 soft symbols (MmParams::q8: nobody asks for the float symbols; SDHIP_MM_Q8=0 turns it off)
+                       MM_FAST = 8,     // fused multiply-adds in the interpolator (MmParams::fast: chunk-parallel mode, SDHIP_FAST_MATH=0 turns it off)
+                       MM_GARD = 16,    // the Gardner loop instead of Mueller & Mueller (MmParams::loop == 1)
+                       MM_TAP = 32,     // tests only: arm positions in place of the symbols (MmParams::tap, sdhip_demod_set_tap)
+                       MM_LIN = 64,     // ndsp::MMClockRecoveryFastBlock's loop on one sequential lane (MmParams::loop == 2)
+                       MM_FEED16 = 128, // the symbol loop runs once per 16 samples instead of 8 (the M&M instances with checkpoints; SDHIP_MM_FEED=8 and SDHIP_COOP_MM=1 keep 8)
+                       MM_UNR = 256;    // the fast paths run three symbols per pass through mm_sym (with MM_FEED16; SDHIP_MM_LOOP=0 keeps the one-symbol loop)
     // CKPT: whenever the block ending at a multiple of MM_CK_SAMPLES samples into its chunk has been fed, a lane leaves a
     // checkpoint {mu, omega, inc, symbols so far}. A re-run lane (exact start state) compares itself with the checkpoint at the
     // same position and stops as soon as it has produced the same number of symbols and is inside the boundary tolerance in
@@ -2735,34 +2736,23 @@ namespace sdhip
     // SPLIT (experimental, SDHIP_MM_SPLIT=1, same results bit for bit -- checked on the host twin; not yet measured): the symbol loop
     // as three plain loops, one per phase, each bounded by a single sample-index test, instead of one loop that re-evaluates the
     // warm-up / chunk / look-ahead bookkeeping (~45 of its ~200 instructions) on every symbol. The lane is issue-bound.
-        // quantiser, module_psk_demod.cpp:199-213 + clamp module_demod_base.h:106-113
-    __device__ __forceinline__ signed char sd_clamp8(float x)
-    {
-        if (x < -128.0f)
-            return -127;
-        if (x > 127.0f)
-            return 127;
-        return (signed char)(int)x;
-    }
-    // the same value without branches (the symbol loop of k_mm<.., Q8>): inside [-128, 127] the conversion truncates as above, beyond 127 the clamp yields 127,
-    // below -128 the select puts -127 where the clamp left -128
-    __device__ __forceinline__ unsigned sd_clamp8_u(float x)
-    {
-        const int r = (int)fminf(fmaxf(x, -128.0f), 127.0f);
-        return (unsigned)(x < -128.0f ? -127 : r) & 0xffu;
-    }
     // FEED: samples moved into the ring per pass of the symbol loop (see block_body / feed_body below): 8, or 16 for the chunk-parallel M&M instances the
     // timed step runs (SDHIP_MM_FEED=8 for A/B; the cooperative loads, Gardner, LIN and the tap keep 8)
     // UNR: the wave-uniform fast paths run their symbols three at a time through mm_sym, without the per-symbol state rotation (the 16-sample feeds'
     // M&M instances; SDHIP_MM_LOOP=0 keeps the one-symbol loop for A/B)
-    template <bool CKPT, bool SPLIT, bool Q8 = false, bool FAST = false, bool GARD = false, bool TAP = false, bool LIN = false, int FEED = 8, bool UNR = false>
+    template <unsigned V>
     __global__ __launch_bounds__(64) void k_mm(const cf32 *x, cf32 *sym, int *counts, ChunkGeom g, MmParams p, const MmState *start0, MmState *spec,
                                                MmState *endst, MmCert *spec_c, MmCert *end_c, const int *redo, int nredo, MmCkpt *ck, int ck_per_chunk,
                                                float ck_tol, int coop_nb)
     {
-        static_assert(FEED == 8 || (!GARD && !LIN && !SPLIT), "longer feeds: the M&M instances only");
-        static_assert(!UNR || (FEED > 8 && !TAP), "the unrolled fast paths: the M&M instances with longer feeds");
-        constexpr int RING = GARD ? MM_RING : mm_ring_mm<FEED>();
+        constexpr bool CKPT = V & MM_CKPT, SPLIT = V & MM_SPLIT, Q8 = V & MM_Q8, FAST = V & MM_FAST, GARD = V & MM_GARD, TAP = V & MM_TAP, LIN = V & MM_LIN, UNR = V & MM_UNR;
+        constexpr int FEED = (V & MM_FEED16) ? 16 : 8;
+        static_assert(!(V & MM_FEED16) || (!GARD && !LIN && !SPLIT), "MM_FEED16: the M&M instances only");
+        static_assert(!UNR || ((V & MM_FEED16) && !TAP), "MM_UNR: the M&M instances with MM_FEED16");
+        static_assert(!SPLIT || !CKPT, "MM_SPLIT: without MM_CKPT");
+        static_assert(!TAP || (CKPT && FAST && !Q8), "MM_TAP: the default float-row instance (MM_CKPT | MM_FAST) only");
+        static_assert(!LIN || V == MM_LIN, "MM_LIN: no other flag");
+        constexpr int RING = GARD ? MM_RING : mm_ring_mm(FEED);
         __shared__ cf32 rings[(RING + MM_MIRROR) * MM_RING_STRIDE];
         __shared__ __attribute__((aligned(16))) float bank[128 * MM_ARM_STRIDE];
         // the transposition buffer of the cooperative loads (load side only: the symbols leave per lane) is DYNAMIC shared memory, there only when a launch uses it
@@ -2920,10 +2910,8 @@ namespace sdhip
                         }
                         else
                         {
-                            const bool fast = wsym < p.fast_syms;
-                            wsym++;
-                            (void)mm_sym<FAST, RING>(mu, om, rel, pn, cn, p1, p2, c1, c2, p, f.ring, roff, lo, bank, fast ? 0.0f : p.omega_gain,
-                                                     fast ? p.mu_gain * p.fast_mult : p.mu_gain);
+                            const bool fast = mm_gear_fast(p, wsym);
+                            (void)mm_sym<FAST, RING>(mu, om, rel, pn, cn, p1, p2, c1, c2, p, f.ring, roff, lo, bank, mm_gear_omega(p, fast), mm_gear_mu(p, fast));
                         }
                 };
                 do
@@ -2954,7 +2942,7 @@ namespace sdhip
         };
         // every symbol whose window ends in front of sample `to` (<= f.next)
         const auto run_syms = [&](const long long to) __attribute__((always_inline)) {
-                if constexpr (SPLIT && !CKPT)
+                if constexpr (SPLIT)
                 {
                     while (!done && s.inc < to)
                     {
@@ -2969,10 +2957,9 @@ namespace sdhip
                             }
                             const long long lim = to < b ? to : b;
                             do
-                            { // warm-up symbols: nothing stored (gear shift: see below)
-                                const bool fast = wsym < p.fast_syms;
-                                wsym++;
-                                (void)mm_iter<false, false, RING>(s, p, f.ring, bank, fast ? 0.0f : p.omega_gain, fast ? p.mu_gain * p.fast_mult : p.mu_gain);
+                            { // warm-up symbols: nothing stored
+                                const bool fast = mm_gear_fast(p, wsym);
+                                (void)mm_iter<false, false, RING>(s, p, f.ring, bank, mm_gear_omega(p, fast), mm_gear_mu(p, fast));
                             } while (s.inc < lim);
                         }
                         else if (phase == 1)
@@ -3042,15 +3029,16 @@ namespace sdhip
                         }
                         while (s.inc < to)
                         {
-                            const bool fast = wsym < p.fast_syms;
-                            wsym++;
-                            (void)clock_iter<GARD, FAST, TAP, RING, LIN>(s, p, f.ring, bank, fast ? 0.0f : p.omega_gain, fast ? p.mu_gain * p.fast_mult : p.mu_gain);
+                            const bool fast = mm_gear_fast(p, wsym);
+                            (void)clock_iter<GARD, FAST, TAP, RING, LIN>(s, p, f.ring, bank, mm_gear_omega(p, fast), mm_gear_mu(p, fast));
                         }
                         return;
                     }
                 }
                 while (!done && s.inc < to)
                 {
+                    // (the two phase transitions are written out here and in the SPLIT loop above: as shared functions or lambdas they change the code the compiler
+                    // makes of every instance -- the timed step's int8 instance: 206 VGPRs instead of 204 -- with nothing measurable gained or lost)
                     if (phase == 0 && s.inc >= b)
                     {
                         spec[k] = s;
@@ -3070,12 +3058,8 @@ namespace sdhip
                         done = true;
                     if (!done)
                     {
-                        // warm-up gear shift: the first fast_syms symbols of a warm-up run with the timing gain raised and the
-                        // rate term frozen (pull-in in ~1/fast_mult of the time), the rest with the loop's own gains so that the
-                        // trajectory settles onto the sequential one; only speculation -- the boundary certificate decides
-                        const bool fast = phase == 0 && wsym < p.fast_syms;
-                        wsym++;
-                        const cf32 v = clock_iter<GARD, FAST, TAP, RING, LIN>(s, p, f.ring, bank, fast ? 0.0f : p.omega_gain, fast ? p.mu_gain * p.fast_mult : p.mu_gain);
+                        const bool fast = mm_gear_fast(p, wsym, phase == 0);
+                        const cf32 v = clock_iter<GARD, FAST, TAP, RING, LIN>(s, p, f.ring, bank, mm_gear_omega(p, fast), mm_gear_mu(p, fast));
                         if (phase != 0)
                         {
                             if (cnt + nx < p.cap)
@@ -3188,12 +3172,10 @@ namespace sdhip
         std::optional<ProfScope> _pr; // the re-run launches (a few lanes, each alone on its SIMD) are part of k_mm's time; listed on their own as well
         if (redo)
             _pr.emplace("k_mm (re-run launches, included in k_mm)", st);
-        const char *split_env = getenv("SDHIP_MM_SPLIT");
-        const bool split = split_env && split_env[0] == '1';
         // cooperative loads of the wave's 64 streams (see Coop): chunk length and warm-up whole 128-byte bursts, at least one full wave of ordinary chunks
         // (measured, visit D of round 5: on these lanes -- latency-bound, one wave per SIMD -- the transposes cost more than the coalescing returns: MetOp 14.6 ms
         // with, 13.3 without at 98 304 lanes; SDHIP_COOP_MM=1 turns it on, tests run both)
-        const bool coop_env = !(getenv("SDHIP_COOP") && atoi(getenv("SDHIP_COOP")) == 0) && getenv("SDHIP_COOP_MM") && atoi(getenv("SDHIP_COOP_MM")) != 0;
+        const bool coop_env = env_int("SDHIP_COOP", 1) != 0 && env_int("SDHIP_COOP_MM", 0) != 0;
         int coop_nb = 0;
         if (coop_env && !redo && g.L % 16 == 0 && g.W % 16 == 0 && g.K >= 66)
             coop_nb = (g.K - 2) / 64;
@@ -3202,81 +3184,78 @@ namespace sdhip
         const int nblk = coop_nb > 0 ? coop_nb + (g.K - 64 * coop_nb + 7) / 8 : (n + 63) / 64;
         if (getenv("SDHIP_DEBUG") && !redo)
             fprintf(stderr, "[sdhip] k_mm: K %d L %d W %d -> %d cooperative blocks of %d\n", g.K, g.L, g.W, coop_nb, nblk);
-        auto go = [&](auto kern, MmCkpt *ckp, int per, float tol) {
-            hipLaunchKernelGGL(kern, dim3(nblk), dim3(64), coop_nb > 0 ? COOP_LDS_BYTES : 0, st, x, sym_scratch, counts, g, p, start0, spec, endst, spec_c, end_c, redo, nredo, ckp, per,
-                               tol, coop_nb);
-        };
+        // the variant (see the MM_* flags at k_mm) from the stage's parameters and the switches
+        unsigned v;
         if (p.tap)
         { // tests only (sdhip_demod_set_tap): the default instance with the arm positions in place of the symbols
             if (!ck || !p.fast || p.q8 || p.loop == 1)
                 throw HipError("the arm tap exists for the chunk-parallel mode's default kernel only");
-            go(k_mm<true, false, false, true, false, true>, ck, ck_per_chunk, ck_tol);
-            return;
+            v = MM_CKPT | MM_FAST | MM_TAP;
         }
-        if (p.loop == 2)
+        else if (p.loop == 2)
         { // ndsp::MMClockRecoveryFastBlock on ONE sequential lane (float symbols): the cadence of its rate updates follows the symbol count (demod_engine.hip, ndsp_create)
             if (g.K != 1 || p.q8 || p.fast || redo)
                 throw HipError("fast_clock_recovery_mm_cc runs as one sequential lane");
-            go(k_mm<false, false, false, false, false, false, true>, nullptr, 0, 0.0f);
-            return;
+            v = MM_LIN;
         }
-        if (p.loop == 1)
+        else if (p.loop == 1)
         { // the Gardner loop on the same lanes (float symbols only)
             if (p.back < 1 || p.back > MM_BACK_MAX || p.q8)
                 throw HipError("Gardner lanes: omega out of the window the lanes carry");
-            if (ck && p.fast)
-                go(k_mm<true, false, false, true, true>, ck, ck_per_chunk, ck_tol);
-            else if (ck)
-                go(k_mm<true, false, false, false, true>, ck, ck_per_chunk, ck_tol);
-            else if (p.fast)
-                go(k_mm<false, false, false, true, true>, nullptr, 0, 0.0f);
-            else
-                go(k_mm<false, false, false, false, true>, nullptr, 0, 0.0f);
-            return;
+            v = MM_GARD | (ck ? MM_CKPT : 0) | (p.fast ? MM_FAST : 0);
         }
-        // the chunk-parallel instances run their symbol loop over 16-sample feeds (SDHIP_MM_FEED=8: over every 8-sample block, as before; same results
-        // bit for bit); the cooperative loads keep 8
-        const char *feed_env = getenv("SDHIP_MM_FEED");
-        const int feed = coop_nb > 0 ? 8 : feed_env ? atoi(feed_env) : 16;
-        if (feed != 8 && feed != 16)
-            throw HipError("SDHIP_MM_FEED: 8 or 16");
-        // their fast paths run three symbols per pass without the state rotation (SDHIP_MM_LOOP=0: one symbol per pass, as before; same results bit for bit)
-        // (mm_sym clips the rate with v_med3_f32: the selects' value for a limit >= 0 -- a negative relative limit keeps the one-symbol loop)
-        const char *loop_env = getenv("SDHIP_MM_LOOP");
-        const int loop_sw = loop_env ? atoi(loop_env) : 1;
-        if (loop_sw != 0 && loop_sw != 1)
-            throw HipError("SDHIP_MM_LOOP: 0 or 1");
-        const bool unr = loop_sw == 1 && p.omega_limit >= 0.0f;
-        if (ck && p.q8 && p.fast && feed == 16 && unr)
-            go(k_mm<true, false, true, true, false, false, false, 16, true>, ck, ck_per_chunk, ck_tol);
-        else if (ck && p.q8 && p.fast && feed == 16)
-            go(k_mm<true, false, true, true, false, false, false, 16>, ck, ck_per_chunk, ck_tol);
-        else if (ck && p.q8 && p.fast)
-            go(k_mm<true, false, true, true>, ck, ck_per_chunk, ck_tol);
-        else if (ck && p.q8 && feed == 16 && unr)
-            go(k_mm<true, false, true, false, false, false, false, 16, true>, ck, ck_per_chunk, ck_tol);
-        else if (ck && p.q8 && feed == 16)
-            go(k_mm<true, false, true, false, false, false, false, 16>, ck, ck_per_chunk, ck_tol);
-        else if (ck && p.q8)
-            go(k_mm<true, false, true>, ck, ck_per_chunk, ck_tol);
-        else if (ck && p.fast && feed == 16 && unr)
-            go(k_mm<true, false, false, true, false, false, false, 16, true>, ck, ck_per_chunk, ck_tol);
-        else if (ck && p.fast && feed == 16)
-            go(k_mm<true, false, false, true, false, false, false, 16>, ck, ck_per_chunk, ck_tol);
-        else if (ck && p.fast)
-            go(k_mm<true, false, false, true>, ck, ck_per_chunk, ck_tol);
-        else if (ck && feed == 16 && unr)
-            go(k_mm<true, false, false, false, false, false, false, 16, true>, ck, ck_per_chunk, ck_tol);
-        else if (ck && feed == 16)
-            go(k_mm<true, false, false, false, false, false, false, 16>, ck, ck_per_chunk, ck_tol);
-        else if (ck)
-            go(k_mm<true, false>, ck, ck_per_chunk, ck_tol);
-        else if (p.q8)
-            go(k_mm<false, false, true>, nullptr, 0, 0.0f);
-        else if (split)
-            go(k_mm<false, true>, nullptr, 0, 0.0f);
         else
-            go(k_mm<false, false>, nullptr, 0, 0.0f);
+        {
+            // the chunk-parallel instances run their symbol loop over 16-sample feeds (SDHIP_MM_FEED=8: over every 8-sample block, as before; same results
+            // bit for bit); the cooperative loads keep 8
+            const int feed = coop_nb > 0 ? 8 : env_int("SDHIP_MM_FEED", 16);
+            if (feed != 8 && feed != 16)
+                throw HipError("SDHIP_MM_FEED: 8 or 16");
+            // their fast paths run three symbols per pass without the state rotation (SDHIP_MM_LOOP=0: one symbol per pass, as before; same results bit for bit)
+            // (mm_sym clips the rate with v_med3_f32: the selects' value for a limit >= 0 -- a negative relative limit keeps the one-symbol loop)
+            const int loop_sw = env_int("SDHIP_MM_LOOP", 1);
+            if (loop_sw != 0 && loop_sw != 1)
+                throw HipError("SDHIP_MM_LOOP: 0 or 1");
+            const bool unr = loop_sw == 1 && p.omega_limit >= 0.0f;
+            if (ck)
+                v = MM_CKPT | (p.q8 ? MM_Q8 : 0) | (p.fast ? MM_FAST : 0) | (feed == 16 ? MM_FEED16 | (unr ? MM_UNR : 0) : 0);
+            else // without checkpoints (exact mode, single blocks, SDHIP_CKPT=0): the 8-sample loop, unfused
+                v = p.q8 ? MM_Q8 : env_int("SDHIP_MM_SPLIT", 0) == 1 ? MM_SPLIT : 0;
+        }
+        const bool ckpt = v & MM_CKPT;
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(nblk), dim3(64), coop_nb > 0 ? COOP_LDS_BYTES : 0, st, x, sym_scratch, counts, g, p, start0, spec, endst, spec_c, end_c, redo, nredo,
+                               ckpt ? ck : nullptr, ckpt ? ck_per_chunk : 0, ckpt ? ck_tol : 0.0f, coop_nb);
+        };
+        // every instance of k_mm, once (DESIGN.md 4 has the table): a variant that is to exist gets its line here
+#define MM_INSTANCE(V) case (V): return go(k_mm<(V)>);
+        switch (v)
+        {
+            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FAST | MM_FEED16 | MM_UNR) // the timed step, int8 rows
+            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FAST | MM_FEED16)
+            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FAST)
+            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FEED16 | MM_UNR)
+            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FEED16)
+            MM_INSTANCE(MM_CKPT | MM_Q8)
+            MM_INSTANCE(MM_CKPT | MM_FAST | MM_FEED16 | MM_UNR) // the timed step, float rows
+            MM_INSTANCE(MM_CKPT | MM_FAST | MM_FEED16)
+            MM_INSTANCE(MM_CKPT | MM_FAST)
+            MM_INSTANCE(MM_CKPT | MM_FEED16 | MM_UNR)
+            MM_INSTANCE(MM_CKPT | MM_FEED16)
+            MM_INSTANCE(MM_CKPT)
+            MM_INSTANCE(MM_Q8)
+            MM_INSTANCE(MM_SPLIT)
+            MM_INSTANCE(0u) // float rows without checkpoints: exact mode, single blocks
+            MM_INSTANCE(MM_CKPT | MM_FAST | MM_TAP)
+            MM_INSTANCE(MM_LIN)
+            MM_INSTANCE(MM_CKPT | MM_FAST | MM_GARD)
+            MM_INSTANCE(MM_CKPT | MM_GARD)
+            MM_INSTANCE(MM_FAST | MM_GARD)
+            MM_INSTANCE(MM_GARD)
+        default:
+            throw HipError("k_mm: no instance for this combination of variant flags");
+        }
+#undef MM_INSTANCE
     }
 
 
