@@ -18,6 +18,20 @@
 #include <mutex>
 #include <vector>
 
+#ifdef SDHIP_HOST_TWIN
+// The host twin runs every launch in place, so one stream is all streams and an event has nothing to order: the calls the two-batch pipeline of
+// process_blocks adds are no-ops there (the pipeline's bookkeeping -- sets, premises, discards -- runs as on the device).
+constexpr unsigned hipEventDisableTiming = 2;
+inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
+inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+inline hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi)
+{
+    *lo = *hi = 0;
+    return hipSuccess;
+}
+inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned flags, int) { return hipStreamCreateWithFlags(s, flags); }
+#endif
+
 namespace sdhip
 {
     static thread_local std::string g_last_error;
@@ -234,6 +248,12 @@ namespace sdhip
         out[i] = o;
     }
 
+    static long long env_int(const char *name, long long dflt)
+    {
+        const char *e = getenv(name);
+        return (e && *e) ? atoll(e) : dflt;
+    }
+
     struct DeframerState
     {
         int state = 2; // numeric thresholds as in bpsk_ccsds_deframer.h:33-35
@@ -246,7 +266,10 @@ namespace sdhip
     struct FecEngine
     {
         sdhip_fec_cfg cfg;
-        hipStream_t stream = nullptr;
+        hipStream_t stream = nullptr;     // everything but an overlapped forward pass
+        hipStream_t stream_fwd = nullptr; // the Viterbi forward passes of process_blocks while two batches are in flight (SDHIP_FEC_OVERLAP)
+        hipEvent_t ev_fwd[2] = {nullptr, nullptr}; // behind the forward pass of the batch in flight set 0 / 1
+        hipEvent_t ev_in = nullptr;       // entry fence: what the caller queued on the legacy default stream (see fence_in)
         int B = 0, F = 0, nber = 0, cadu_bytes = 0, wpb = 0, dstride = 0;
         VitCfg vc{};
         int phases[4] = {0, 0, 0, 0};
@@ -371,6 +394,17 @@ namespace sdhip
         DevBuf<VitBlockIO> d_io;
         DevBuf<uint64_t> d_dec;
         Vit2Work vit2;
+        // what two batches in flight cannot share, second set (the members above / below are the first): control words, decision records, decoded bits
+        struct VitFlight
+        {
+            DevBuf<VitBlockIO> d_io;
+            PinBuf<VitBlockIO> h_io;
+            DevBuf<uint32_t> d_vbits;
+            Vit2Work vit2;
+        } alt;
+        Vit2Work vit2_one;                     // one block decoded again on its own (a batch issued ahead whose guessed start state was wrong)
+        DevBuf<uint64_t> d_dec_redo;           // decision scratch of the re-decode rounds (d_dec may belong to a forward pass in flight)
+        const uint32_t *def_vbits = nullptr;   // decoded bits the deframer reads, when they are not d_vbits
         std::vector<int> redo_list;
         DevBuf<int> d_redo;
         bool use_vit2 = !(getenv("SDHIP_VIT2") && atoi(getenv("SDHIP_VIT2")) == 0);
@@ -401,7 +435,19 @@ namespace sdhip
         explicit FecEngine(const sdhip_fec_cfg &c) : cfg(c)
         {
             SD_HIP(hipSetDevice(cfg.device));
-            SD_HIP(hipStreamCreate(&stream));
+            // Neither stream takes part in the legacy default stream's implicit ordering: a forward pass must not wait for (or hold up) whatever else the
+            // process has queued there. What the caller queued there BEFORE a call is waited for explicitly (fence_in).
+            // `stream`, which carries the short kernels behind a forward pass, at the highest priority: at equal priority their workgroups queue behind the
+            // forward pass's and the tail does not get under it (measured). SDHIP_FEC_TAIL_PRIO=0 (read once, here): equal priorities.
+            {
+                int lo = 0, hi = 0;
+                SD_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+                SD_HIP(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, env_int("SDHIP_FEC_TAIL_PRIO", 1) != 0 ? hi : 0));
+                SD_HIP(hipStreamCreateWithFlags(&stream_fwd, hipStreamNonBlocking));
+                for (hipEvent_t &e : ev_fwd)
+                    SD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                SD_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
+            }
             if (cfg.cadu_size <= 32 || cfg.cadu_size % 8 != 0)
                 throw HipError("cadu_size must be a multiple of 8 bits (padded frames are not supported by the HIP path)");
             cadu_bytes = cfg.cadu_size / 8;
@@ -614,8 +660,27 @@ namespace sdhip
         }
         ~FecEngine()
         {
+            if (stream_fwd)
+            {
+                (void)hipStreamSynchronize(stream_fwd);
+                (void)hipStreamDestroy(stream_fwd);
+            }
             if (stream)
                 (void)hipStreamDestroy(stream);
+            for (hipEvent_t e : ev_fwd)
+                if (e)
+                    (void)hipEventDestroy(e);
+            if (ev_in)
+                (void)hipEventDestroy(ev_in);
+        }
+
+        // The engine's streams do not synchronise with the legacy default stream by themselves. A caller that filled the input (or zeroed the output) there
+        // -- PyTorch's default stream is that stream -- relied on it: every entry point waits here for what is queued there at this moment.
+        void fence_in()
+        {
+            SD_HIP(hipEventRecord(ev_in, nullptr));
+            SD_HIP(hipStreamWaitEvent(stream, ev_in, 0));
+            SD_HIP(hipStreamWaitEvent(stream_fwd, ev_in, 0));
         }
 
         void upload_carry()
@@ -881,7 +946,7 @@ namespace sdhip
                 BitStream bs;
                 bs.carry = d_carry[carry_sel].p;
                 bs.carry_bits = carry_bits;
-                bs.vbits = d_vbits.p;
+                bs.vbits = def_vbits ? def_vbits : d_vbits.p;
                 bs.F = F;
                 bs.wpb = wpb;
                 bs.nblk = n_eff;
@@ -917,7 +982,10 @@ namespace sdhip
                     hits.resize(count);
                     if (count)
                     {
-                        SD_HIP(hipMemcpy(hits.data(), d_hits.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+                        h_hits.reserve(count);
+                        SD_HIP(hipMemcpyAsync(h_hits.p, d_hits.p, (size_t)count * 4, hipMemcpyDeviceToHost, stream));
+                        SD_HIP(hipStreamSynchronize(stream));
+                        memcpy(hits.data(), h_hits.p, (size_t)count * 4);
                         for (auto &h : hits)
                             h += (uint32_t)(from << 1);
                         std::sort(hits.begin(), hits.end());
@@ -1751,13 +1819,17 @@ namespace sdhip
         // Decodes blocks [pos, pos + n) of d_soft under `vc` into d_vbits (packed) and leaves every block's control words -- start / end / chained
         // state, BER sums, encoder register -- in h_io. Speculation (segment warm-ups, start states taken from the previous block's tail) is
         // verified here; what fails is decoded again.
-        void vit_run(const VitCfg &vc, const int8_t *d_soft, int64_t pos, int n, int first_start_in, DevBuf<VitBlockIO> &d_io, PinBuf<VitBlockIO> &h_io,
-                     DevBuf<uint32_t> &d_vbits, unsigned enc_state_in, const std::function<void(const char *)> &tick)
+        // Two halves, so that process_blocks can run the next batch's forward pass under this batch's tail: vit_issue uploads the control words and
+        // launches the forward pass on `st`; vit_finish launches what reads its records on `stream`, waits, and verifies. A batch in flight owns its
+        // d_io / h_io / d_vbits / Vit2Work until its vit_finish has returned.
+        void vit_issue(const VitCfg &vc, const int8_t *d_soft, int64_t pos, int n, int first_start_in, DevBuf<VitBlockIO> &d_io, PinBuf<VitBlockIO> &h_io,
+                       DevBuf<uint32_t> &d_vbits, Vit2Work &w, hipStream_t st)
         {
             const int wpb = vit_words_per_block(vc.F), dstride = (vc.F + 6 + 63) / 64 * 64; // of THIS decoder (the FengYun rails are not the engine's F)
             d_io.reserve(n);
             h_io.reserve(n);
-            if (!(use_vit2 && vit2_supported(vc)))
+            const bool v2 = use_vit2 && vit2_supported(vc);
+            if (!v2)
                 d_dec.reserve((size_t)n * dstride);
             d_vbits.reserve((size_t)n * wpb + 4);
             for (int j = 0; j < n; j++)
@@ -1766,12 +1838,21 @@ namespace sdhip
                 h_io.p[j].start_in = -1;
             }
             h_io.p[0].start_in = first_start_in;
-            SD_HIP(hipMemcpyAsync(d_io.p, h_io.p, (size_t)n * sizeof(VitBlockIO), hipMemcpyHostToDevice, stream));
+            SD_HIP(hipMemcpyAsync(d_io.p, h_io.p, (size_t)n * sizeof(VitBlockIO), hipMemcpyHostToDevice, st));
+            if (v2)
+                launch_vit_decode2(vc, d_soft, pos, n, d_io.p, d_vbits.p, w, st, VIT2_FORWARD);
+            else
+                launch_vit_decode(vc, d_soft, pos, n, d_io.p, d_dec.p, d_vbits.p, st); // (forward pass and traceback are one kernel there)
+        }
+        // chain_in >= 0: the batch was issued before the previous one had been verified, its block 0 with start_in = -1 like an inner block; chain_in is the
+        // start state the previous batch's last block handed on, now that it is known. The chain certificate below extends across the batch boundary with it.
+        void vit_finish(const VitCfg &vc, const int8_t *d_soft, int64_t pos, int n, int chain_in, DevBuf<VitBlockIO> &d_io, PinBuf<VitBlockIO> &h_io,
+                        DevBuf<uint32_t> &d_vbits, Vit2Work &w, unsigned enc_state_in, const std::function<void(const char *)> &tick)
+        {
+            const int dstride = (vc.F + 6 + 63) / 64 * 64;
             const bool v2 = use_vit2 && vit2_supported(vc);
             if (v2)
-                launch_vit_decode2(vc, d_soft, pos, n, d_io.p, d_vbits.p, vit2, stream);
-            else
-                launch_vit_decode(vc, d_soft, pos, n, d_io.p, d_dec.p, d_vbits.p, stream);
+                launch_vit_decode2(vc, d_soft, pos, n, d_io.p, d_vbits.p, w, stream, VIT2_FINISH);
             // The BER estimate of every block right behind the decode, on the assumption that no block has to be decoded again (the rule by far): ONE copy of the
             // control words and one wait instead of two (3.3 MB and a round trip per 65 536-block batch, with the device idle: 0.28 ms of a MetOp step). A block
             // that fails a certificate below is decoded again and the estimate taken again, as before.
@@ -1779,6 +1860,27 @@ namespace sdhip
             SD_HIP(hipMemcpyAsync(h_io.p, d_io.p, (size_t)n * sizeof(VitBlockIO), hipMemcpyDeviceToHost, stream));
             SD_HIP(hipStreamSynchronize(stream));
             bool ber_valid = true;
+            unsigned n_bound = 0;
+            if (chain_in >= 0 && h_io.p[0].start_used != chain_in)
+            {
+                // The guess for block 0 was wrong: the block again, on its own, by the decoder and with the segment length of its batch and from the start state
+                // the serial order would have given it -- its bits, its certificate and its traceback counters are then what that order produces, and the
+                // rounds below treat it like any other block. (Not booked as a start-state re-decode: the serial order has none here.)
+                n_bound = 1;
+                ber_valid = false;
+                h_io.p[0] = VitBlockIO{};
+                h_io.p[0].start_in = chain_in;
+                SD_HIP(hipMemcpyAsync(d_io.p, h_io.p, sizeof(VitBlockIO), hipMemcpyHostToDevice, stream));
+                if (v2)
+                    launch_vit_decode2(vc, d_soft, pos, 1, d_io.p, d_vbits.p, vit2_one, stream, VIT2_BOTH, n);
+                else
+                {
+                    d_dec_redo.reserve((size_t)dstride);
+                    launch_vit_decode(vc, d_soft, pos, 1, d_io.p, d_dec_redo.p, d_vbits.p, stream);
+                }
+                SD_HIP(hipMemcpyAsync(h_io.p, d_io.p, sizeof(VitBlockIO), hipMemcpyDeviceToHost, stream));
+                SD_HIP(hipStreamSynchronize(stream));
+            }
             // Certificates, in rounds (every failing block of a round is decoded again in ONE launch of the
             // wave-per-block kernel, which is exact within a block given its start state): (1) segment certificate of
             // the lane-per-segment kernel failed (tb_fallback == 2) -> again from the start state it used; (2) the
@@ -1809,10 +1911,10 @@ namespace sdhip
                     throw HipError("viterbi start-state chain does not converge");
                 const int nr = (int)redo_list.size();
                 d_redo.reserve(nr);
-                d_dec.reserve((size_t)nr * dstride);
+                d_dec_redo.reserve((size_t)nr * dstride);
                 SD_HIP(hipMemcpyAsync(d_redo.p, redo_list.data(), (size_t)nr * sizeof(int), hipMemcpyHostToDevice, stream));
                 SD_HIP(hipMemcpyAsync(d_io.p, h_io.p, (size_t)n * sizeof(VitBlockIO), hipMemcpyHostToDevice, stream));
-                launch_vit_decode(vc, d_soft, pos, nr, d_io.p, d_dec.p, d_vbits.p, stream, d_redo.p);
+                launch_vit_decode(vc, d_soft, pos, nr, d_io.p, d_dec_redo.p, d_vbits.p, stream, d_redo.p);
                 SD_HIP(hipMemcpyAsync(h_io.p, d_io.p, (size_t)n * sizeof(VitBlockIO), hipMemcpyDeviceToHost, stream));
                 SD_HIP(hipStreamSynchronize(stream));
             }
@@ -1823,8 +1925,8 @@ namespace sdhip
                 n_tbfb += h_io.p[j].tb_fallback;
             stats.tb_respec += n_tbfb;
             if (getenv("SDHIP_DEBUG"))
-                fprintf(stderr, "[sdhip] viterbi batch %d blocks (%s): segment-certificate re-decodes %u, start-state re-decodes %u in %u round(s), serial tracebacks %u\n", n,
-                        v2 ? "lane-per-segment" : "wave-per-block", n_cert, n_chain, n_rounds, n_tbfb);
+                fprintf(stderr, "[sdhip] viterbi batch %d blocks (%s): segment-certificate re-decodes %u, start-state re-decodes %u in %u round(s), serial tracebacks %u, batch-boundary re-decodes %u\n", n,
+                        v2 ? "lane-per-segment" : "wave-per-block", n_cert, n_chain, n_rounds, n_tbfb, n_bound);
             tick("viterbi");
             // BER estimate of every block (taken above unless something was decoded again), then the lock FSM (viterbi_1_2.cpp:101-113)
             if (!ber_valid)
@@ -1833,6 +1935,12 @@ namespace sdhip
                 SD_HIP(hipMemcpyAsync(h_io.p, d_io.p, (size_t)n * sizeof(VitBlockIO), hipMemcpyDeviceToHost, stream));
                 SD_HIP(hipStreamSynchronize(stream));
             }
+        }
+        void vit_run(const VitCfg &vc, const int8_t *d_soft, int64_t pos, int n, int first_start_in, DevBuf<VitBlockIO> &d_io, PinBuf<VitBlockIO> &h_io,
+                     DevBuf<uint32_t> &d_vbits, unsigned enc_state_in, const std::function<void(const char *)> &tick)
+        {
+            vit_issue(vc, d_soft, pos, n, first_start_in, d_io, h_io, d_vbits, vit2, stream);
+            vit_finish(vc, d_soft, pos, n, -1, d_io, h_io, d_vbits, vit2, enc_state_in, tick);
         }
 
         // ------------------------------------------------------------------ fengyun_ahrpt_decoder
@@ -1990,15 +2098,32 @@ namespace sdhip
 
         void process_blocks(const int8_t *d_soft, int64_t nblocks, uint8_t *d_out, size_t out_cap_frames, size_t &out_written)
         {
+            fence_in();
             if (cfg.decoder == SDHIP_DEC_FENGYUN_AHRPT || cfg.decoder == SDHIP_DEC_FENGYUN_MPT)
                 return process_blocks_fengyun(d_soft, nblocks, d_out, out_cap_frames, out_written);
             if (cfg.decoder == SDHIP_DEC_SIMPLE_PSK)
                 return process_blocks_simple(d_soft, nblocks, d_out, out_cap_frames, out_written);
             if (punc.rate != 0)
                 return process_blocks_punctured(d_soft, nblocks, d_out, out_cap_frames, out_written);
+            // Software pipeline over the batches of a locked stream (SDHIP_FEC_OVERLAP, default on): before the host turns to batch i's tail -- traceback,
+            // certificates, BER estimate, lock FSM, deframer, RS, each with its round trips -- it queues batch i+1's forward pass on stream_fwd. The forward
+            // pass leaves half of every SIMD's registers and nearly all of the HBM bandwidth unused, which is what the tail's kernels need. A batch issued
+            // ahead rests on the premise that batch i is accepted whole and the decoder stays locked; where that fails (the FSM drops lock, the MetOp
+            // watchdog cuts the run) it is drained and discarded, and the loop goes on from the new `pos` as the serial order does. 0 = one batch at a time.
+            const bool overlap = env_int("SDHIP_FEC_OVERLAP", 1) != 0;
+            hipStream_t sf = overlap ? stream_fwd : stream;
+            // even batches: the share of the tails that can be hidden is (N-1)/N of N equal batches, and the last batch is not an odd short one
+            auto batch_at = [&](int64_t at) -> int {
+                const int64_t left = nblocks - at, nb = (left + max_batch - 1) / max_batch;
+                return (int)((left + nb - 1) / nb);
+            };
             int64_t pos = 0;
             tap_ber.reserve(tap_ber.size() + nblocks);
             tap_state.reserve(tap_state.size() + nblocks);
+            int cur = 0;        // set of buffers of the batch at hand (0: the engine's own members, 1: alt)
+            int ahead_n = 0;    // > 0: the batch at `pos` is in flight already, in set `cur`, this many blocks
+            try
+            {
             while (pos < nblocks)
             {
                 if (vstate == 0)
@@ -2024,16 +2149,39 @@ namespace sdhip
                     fprintf(stderr, "[sdhip] fec   %-10s %7.3f ms (host wall)\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
                     t_prev = t;
                 };
-                const int n = (int)std::min<int64_t>(nblocks - pos, max_batch);
-                vc.iq_swap = v_iq_swap;
-                vc.phase = v_phase;
-                vc.shift = v_shift;
-                vit_run(vc, d_soft, pos, n, dec_first ? -2 : dec_start, d_io, h_io, d_vbits, search.enc_state, tick);
+                DevBuf<VitBlockIO> &c_dio = cur ? alt.d_io : d_io;
+                PinBuf<VitBlockIO> &c_hio = cur ? alt.h_io : h_io;
+                DevBuf<uint32_t> &c_vb = cur ? alt.d_vbits : d_vbits;
+                Vit2Work &c_w = cur ? alt.vit2 : vit2;
+                const bool was_ahead = ahead_n > 0;
+                const int n = was_ahead ? ahead_n : batch_at(pos);
+                ahead_n = 0;
+                if (!was_ahead)
+                {
+                    vc.iq_swap = v_iq_swap;
+                    vc.phase = v_phase;
+                    vc.shift = v_shift;
+                    vit_issue(vc, d_soft, pos, n, dec_first ? -2 : dec_start, c_dio, c_hio, c_vb, c_w, sf);
+                    if (overlap)
+                        SD_HIP(hipEventRecord(ev_fwd[cur], sf));
+                }
+                if (overlap)
+                    SD_HIP(hipStreamWaitEvent(stream, ev_fwd[cur], 0)); // the tail of this batch behind its forward pass
+                // the next batch's forward pass, behind this one's on the same stream; its block 0 takes its start state from the tail of this batch's last
+                // block in d_soft, like every inner block (start_in = -1), and vit_finish checks that guess against dec_start once this batch has given it
+                int next_n = 0;
+                if (overlap && pos + n < nblocks)
+                {
+                    next_n = batch_at(pos + n);
+                    vit_issue(vc, d_soft, pos + n, next_n, -1, cur ? d_io : alt.d_io, cur ? h_io : alt.h_io, cur ? d_vbits : alt.d_vbits, cur ? vit2 : alt.vit2, sf);
+                    SD_HIP(hipEventRecord(ev_fwd[cur ^ 1], sf));
+                }
+                vit_finish(vc, d_soft, pos, n, was_ahead ? dec_start : -1, c_dio, c_hio, c_vb, c_w, search.enc_state, tick);
                 int accepted = n;
                 const size_t tap0 = tap_ber.size();
                 for (int j = 0; j < n; j++)
                 {
-                    const float errors = (float)h_io.p[j].ber_err, total = (float)h_io.p[j].ber_tot;
+                    const float errors = (float)c_hio.p[j].ber_err, total = (float)c_hio.p[j].ber_tot;
                     v_ber = (float)((errors / total) * ber_mult);
                     if (v_ber > cfg.viterbi_ber_thresold)
                     {
@@ -2053,7 +2201,9 @@ namespace sdhip
                 }
                 tick("ber+fsm");
                 // hand the accepted blocks to the deframer (the MetOp watchdog may cut the run shorter)
+                def_vbits = c_vb.p;
                 const int used = deframe_and_emit(accepted, d_out, out_cap_frames, out_written);
+                def_vbits = nullptr;
                 tick("deframe+rs");
                 if (used < accepted)
                 { // MetOp watchdog reset the Viterbi after block used-1: the rest of the run is decoded again after re-lock
@@ -2062,10 +2212,28 @@ namespace sdhip
                     tap_state.resize(tap0 + accepted);
                 }
                 dec_first = 0;
-                dec_start = h_io.p[accepted - 1].ret_state;
-                search.enc_state = (unsigned)h_io.p[accepted - 1].pad;
+                dec_start = c_hio.p[accepted - 1].ret_state;
+                search.enc_state = (unsigned)c_hio.p[accepted - 1].pad;
                 pos += accepted;
                 stats.blocks += accepted;
+                if (next_n > 0)
+                {
+                    if (accepted < n || vstate == 0)
+                        SD_HIP(hipStreamSynchronize(stream_fwd)); // issued on a wrong premise: drained, never read; the next issue starts its set afresh
+                    else
+                    {
+                        ahead_n = next_n;
+                        cur ^= 1;
+                    }
+                }
+            }
+            }
+            catch (...)
+            { // nothing of this call stays in flight or selected behind an error
+                def_vbits = nullptr;
+                (void)hipStreamSynchronize(stream_fwd);
+                (void)hipStreamSynchronize(stream);
+                throw;
             }
             stats.viterbi_lock = vstate;
             stats.viterbi_ber = current_ber();
@@ -2136,6 +2304,7 @@ namespace sdhip
         // append n bytes (device or host memory) to the raw stream kept on the device; bytes no gather can reach any more are dropped first
         void m2x_append(const int8_t *src, size_t n, bool on_device)
         {
+            fence_in();
             // the oldest call an output of a future call can still come from: 35 x 73 728 data samples = 316 calls back
             long long keep_from = m2x.raw_end;
             for (const M2xBranch &b : m2x.br)

@@ -73,8 +73,13 @@ namespace sdhip
         DevBuf<int> entry, exitst;  // traceback hand-off states per unit
     };
     inline bool vit2_supported(const VitCfg &cfg) { return cfg.F >= 2 * VIT2_SEG && cfg.F % VIT2_SEG == 0; }
+    // phase: the forward pass (symbol rows + ACS: everything that fills `w`) and what follows it (traceback + certificate, which read `w` and write
+    // vbits / io) can be launched apart, on different streams, so that the next batch's forward pass runs under this batch's tail. The two calls of a
+    // batch take the same arguments. seg_nblk > 0: choose the segment length as for a batch of that many blocks (a block decoded again on its own
+    // then gets the segments, and so the certificate, it had inside its batch).
+    enum { VIT2_BOTH = 0, VIT2_FORWARD = 1, VIT2_FINISH = 2 };
     void launch_vit_decode2(const VitCfg &cfg, const int8_t *soft, int64_t first_block, int nblk, VitBlockIO *io, uint32_t *vbits, Vit2Work &w,
-                            hipStream_t st);
+                            hipStream_t st, int phase = VIT2_BOTH, int seg_nblk = 0);
 
     // BER estimate of every block (viterbi_1_2.cpp:101-102 / viterbi_3_4.cpp:156-157): re-encode the first
     // nber decoded bits (encoder register chained through the previous block, enc_state_in for block 0) and

@@ -1511,10 +1511,13 @@ namespace sdhip
         io[j].tb_fallback = fail ? 2 : 0;
     }
 
-    void launch_vit_decode2(const VitCfg &cfg, const int8_t *soft, int64_t first_block, int nblk, VitBlockIO *io, uint32_t *vbits, Vit2Work &w, hipStream_t st)
+    void launch_vit_decode2(const VitCfg &cfg, const int8_t *soft, int64_t first_block, int nblk, VitBlockIO *io, uint32_t *vbits, Vit2Work &w, hipStream_t st, int phase,
+                            int seg_nblk)
     {
         if (nblk <= 0)
             return;
+        const bool do_fwd = phase != VIT2_FINISH, do_fin = phase != VIT2_FORWARD;
+        const long long rule_nblk = seg_nblk > 0 ? seg_nblk : nblk;
         // segment length: 512 steps; two or four times that when the batch still fills the chip with >= 2 waves per SIMD (the 200-step
         // warm-up then costs 20 % / 10 % instead of 39 %)
         const int F = cfg.F;
@@ -1525,7 +1528,7 @@ namespace sdhip
                 S = atoi(e);
             else
                 for (int m = 4; m >= 2; m >>= 1) // 2048, then 1024 steps per lane (measured, MetOp / NPP 17 GB: 12.8 / 11.2 ms at 1024, 12.5 / 10.7 at 2048, 14.4 at 512)
-                    if (F % (m * VIT2_SEG) == 0 && F / (m * VIT2_SEG) >= 2 && (long long)nblk * (F / (m * VIT2_SEG)) >= 2 * 65536)
+                    if (F % (m * VIT2_SEG) == 0 && F / (m * VIT2_SEG) >= 2 && rule_nblk * (F / (m * VIT2_SEG)) >= 2 * 65536)
                     {
                         S = m * VIT2_SEG;
                         break;
@@ -1534,15 +1537,18 @@ namespace sdhip
         const int NSEG = F / S;
         const int SU = (VIT2_WARM + F + 6 + 8 + 7) / 8 * 8; // one spare group: the forward pass prefetches 8 steps ahead
         const long long U = (long long)nblk * NSEG, U64 = (U + 63) / 64 * 64;
-        w.dec.reserve((size_t)(S + 8) * U64);
-        w.specx.reserve((size_t)U * 32);
-        w.endx.reserve((size_t)U * 32);
-        w.entry.reserve((size_t)U);
-        w.exitst.reserve((size_t)U);
+        if (do_fwd)
+        { // (the finish half works on what the forward half of the same batch reserved)
+            w.dec.reserve((size_t)(S + 8) * U64);
+            w.specx.reserve((size_t)U * 32);
+            w.endx.reserve((size_t)U * 32);
+            w.entry.reserve((size_t)U);
+            w.exitst.reserve((size_t)U);
+        }
         const int wpb = vit_words_per_block(F);
         const bool hist = !(getenv("SDHIP_VIT2_HIST") && atoi(getenv("SDHIP_VIT2_HIST")) == 0); // A/B switch: 0 = per-step decision words (k_vit2_acs / k_vit2_tb)
         const bool fused = hist && !(getenv("SDHIP_VIT2_FUSED") && atoi(getenv("SDHIP_VIT2_FUSED")) == 0); // A/B switch: 0 = k_vit2_prep writes the rows first
-        if (!fused)
+        if (!fused && do_fwd)
         {
             w.symu.reserve((size_t)nblk * SU + 64);
             ProfScope _ps("k_vit2_prep", st);
@@ -1564,6 +1570,7 @@ namespace sdhip
         }
         if (hist)
         {
+            if (do_fwd)
             {
                 ProfScope _ps("k_vit2_acs", st);
                 auto go = [&](auto kern) {
@@ -1585,6 +1592,7 @@ namespace sdhip
                 default: go(k_vit2h_acs<-1, -1, false>); break;
                 }
             }
+            if (do_fin)
             {
                 ProfScope _ps("k_vit2_tb", st);
                 hipLaunchKernelGGL(k_vit2h_tb, dim3((unsigned)(U64 / 64)), dim3(64), 0, st, F, S, NSEG, nblk, io, (const uint4 *)w.dec.p, U64, vbits, wpb, w.entry.p, w.exitst.p);
@@ -1592,17 +1600,20 @@ namespace sdhip
         }
         else
         {
+            if (do_fwd)
             {
                 ProfScope _ps("k_vit2_acs", st);
                 hipLaunchKernelGGL(k_vit2_acs, dim3((unsigned)(U64 / 64)), dim3(64), 0, st, F, S, NSEG, nblk, w.symu.p, SU, io, (unsigned long long *)w.dec.p, U64,
                                    w.specx.p, w.endx.p);
             }
+            if (do_fin)
             {
                 ProfScope _ps("k_vit2_tb", st);
                 hipLaunchKernelGGL(k_vit2_tb, dim3((unsigned)(U64 / 64)), dim3(64), 0, st, F, S, NSEG, nblk, io, (const unsigned long long *)w.dec.p, U64, vbits, wpb,
                                    w.entry.p, w.exitst.p);
             }
         }
+        if (do_fin)
         {
             ProfScope _ps("k_vit2_cert", st);
             hipLaunchKernelGGL(k_vit2_cert, dim3((nblk + 63) / 64), dim3(64), 0, st, NSEG, nblk, w.specx.p, w.endx.p, w.entry.p, w.exitst.p, io);
