@@ -168,6 +168,29 @@ extern "C"
        output is a by-product). Destroy with sdhip_demod_destroy. */
     void *sdhip_dvbs2_front_create(const sdhip_demod_cfg *cfg);
 
+    /* ---- fsk_demod / sdpsk_demod: the real-valued demodulators (src-core/pipeline/modules/demod/module_fsk_demod.cpp:59-84,133-134, module_sdpsk_demod.cpp:56-71,
+       119-120). BaseDemodModule's chain up to and including its complex AGC -- formats, iq_swap, dc_block, freq_shift, Doppler, custom_samplerate, the resample
+       decision: the psk_demod handle's own code -- then QuadratureDemodBlock(1) -> CorrectIQBlock<float> -> [fsk only: AGCBlock<float>(0.1, 0.5, 1, 65535)] ->
+       FIRBlock<float> (the RRC taps, or with basic_shaping one tap of 0.1 per `for (i = 0; i < final_sps; i++)`) -> MMClockRecoveryBlock<float> ->
+       clamp(sym * 50) (fsk) / clamp(sym * 400) (sdpsk). Same configuration struct (rrc_alpha is mandatory unless basic_shaping is set; constellation, pll_bw,
+       has_carrier and post_costas_dc are not read), same handle functions: sdhip_demod_push / flush / pull / process_dev / get_stats / doppler_targets /
+       destroy. Output: ONE int8 per symbol; with d_syms != NULL the float symbols leave as ONE float per symbol and syms_cap counts symbols. exact = 1: one
+       sequential lane per recurrence, bit for bit the reference's blocks; exact = 0: the chunk-parallel schedule. Stream state carries across calls. */
+    enum
+    {
+        SDHIP_REAL_FSK = 0,  /* "fsk_demod"   */
+        SDHIP_REAL_SDPSK = 1 /* "sdpsk_demod" */
+    };
+    typedef struct sdhip_fsk_ext
+    {
+        int kind;          /* SDHIP_REAL_FSK / SDHIP_REAL_SDPSK */
+        int basic_shaping; /* "basic_shaping" (fsk_demod only), default 0 */
+    } sdhip_fsk_ext;
+    /* the MODULE's defaults (module_fsk_demod.h:25-31, module_sdpsk_demod.h:23-29 and the constructors): clock gains from 1.7e-2, rrc_taps 31,
+       MIN_SPS / MAX_SPS 1.0 / 10.0 for sdpsk */
+    void sdhip_fsk_cfg_default(int kind, sdhip_demod_cfg *cfg, sdhip_fsk_ext *ext);
+    void *sdhip_fsk_demod_create(const sdhip_demod_cfg *cfg, const sdhip_fsk_ext *ext); /* NULL on error */
+
     /* ---- ndsp: the reference's new block API -------------------------
        satdump::ndsp::PSKDemodHierBlock (src-core/dsp/hier/psk_demod.h:22-249, psk_demod.cpp:8-14): RRC FIR -> AGC (reference 0.6) ->
        M&M clock recovery -> Costas loop at ONE sample per symbol, complex symbols out; no resampler, no quantiser. The fields are the
@@ -340,6 +363,11 @@ extern "C"
        9 ndsp Costas(bw,order,limit) dsp/pll/costas.cpp:12-61 (branched clip) | 10 ndsp Gardner(omega,gw,mu,gmu,lim)
        dsp/clock_recovery/clock_recovery_gardner.cpp:60-170 (kind 7 with branched clips on floats). The other ndsp blocks compute what kinds 0, 1 and 3 do
        (dsp/agc/agc.cpp:22-39, dsp/filter/fir.cpp:62-133 minus its ntaps-sample latency, dsp/clock_recovery/clock_recovery_mm.cpp:66-183).
+       The real-valued blocks of fsk_demod / sdpsk_demod (float samples in and out, but for kind 11's complex input); each takes ONE MORE parameter behind its own,
+       `cont`: 0 = a new stream, 1 = the call continues the stream of the previous call of that kind (the block's state is kept inside the library):
+       11 QuadratureDemod(gain) quadrature_demod.cpp:36-48 | 12 CorrectIQ<float>() correct_iq.cpp:27-31 | 13 AGC<float>(rate,ref,gain,max) agc.cpp:25-39 |
+       14 FIR<float>(fs,symrate,alpha,ntaps,nbox) fir.cpp:59-71 -- the RRC taps, or with nbox > 0 that many taps of 0.1 |
+       15 MM<float>(omega,gw,mu,gmu,lim) clock_recovery_mm.cpp:70-88,111-120.
        Returns output sample count. */
     int64_t sdhip_op_block(int device, int kind, const float *params, const float *d_in, size_t n, float *d_out, size_t out_cap);
 

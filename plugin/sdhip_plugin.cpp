@@ -6,6 +6,7 @@
 //   metop_ahrpt_decoder_hip        <- MetOpAHRPTDecoderModule      (plugins/noaa_metop_support/metop/module_metop_ahrpt_decoder.{h,cpp})
 //   ccsds_simple_psk_decoder_hip   <- CCSDSSimplePSKDecoderModule  (src-core/pipeline/modules/ccsds/module_ccsds_simple_psk_decoder.{h,cpp})
 //   dvbs2_demod_hip                <- DVBS2DemodModule             (plugins/dvb_support/dvbs2/module_dvbs2_demod.{h,cpp})
+//   fsk_demod_hip / sdpsk_demod_hip <- FSKDemodModule / SDPSKDemodModule (src-core/pipeline/modules/demod/module_fsk_demod.{h,cpp}, module_sdpsk_demod.{h,cpp})
 // during RegisterModulesEvent (src-core/pipeline/module.h:213-216) and, when SDHIP_OVERRIDE=1 is set, re-points the
 // reference ids themselves at these classes from a SatDumpStartedEvent handler (src-core/core/plugin.h:21-23; the
 // registry lookup is first-match, src-core/pipeline/module.cpp:129-135), so existing pipelines run unchanged.
@@ -767,6 +768,226 @@ namespace sdhip_plugin
             return std::make_shared<PSKDemodHipModule>(input_file, output_file_hint, parameters);
         }
     };
+
+    // ---------------------------------------------------------------------------------- fsk_demod / sdpsk_demod
+    // FSKDemodModule / SDPSKDemodModule (src-core/pipeline/modules/demod/module_fsk_demod.{h,cpp}, module_sdpsk_demod.{h,cpp}) on the HIP path: psk_demod_hip's
+    // file / FIFO / dsp::stream loops and container readers around a handle of sdhip_fsk_demod_create. One int8 per symbol leaves for the .soft file / the FIFO.
+    // Doppler correction and hip_devices are not this module's: such parameter sets stay with the CPU module (covers()).
+    template <int KIND>
+    class RealDemodHipModule : public ProcessingModule
+    {
+        sdhip_demod_cfg cfg;
+        sdhip_fsk_ext ext;
+        void *h = nullptr;
+        std::string baseband_format = "cf32";
+        int fmt = SDHIP_FMT_CF32;
+        std::atomic<uint64_t> filesize{0}, progress{0};
+        std::atomic<float> snr{0}, peak_snr{0};
+        std::atomic<bool> should_stop{false};
+        std::ofstream data_out;
+        static const char *who() { return KIND == SDHIP_REAL_FSK ? "fsk_demod_hip" : "sdpsk_demod_hip"; }
+        // M2M4 estimate on PAIRS of soft symbols, the way the modules hand their float symbols to M2M4SNREstimator as complex numbers
+        // (module_fsk_demod.cpp:126-127: update((complex_t *)readBuf, dat_size / 2)); informative, not part of the data path
+        float snr_y1 = 0, snr_y2 = 0;
+        void snr_update(const int8_t *soft, size_t n)
+        {
+            const float sc = KIND == SDHIP_REAL_FSK ? 1.0f / 50.0f : 1.0f / 400.0f, alpha = 0.001f, beta = 1.0f - alpha;
+            for (size_t i = 0; i + 1 < n; i += 2)
+            {
+                const float re = soft[i] * sc, im = soft[i + 1] * sc;
+                const float m2 = re * re + im * im;
+                snr_y1 = alpha * m2 + beta * snr_y1;
+                snr_y2 = alpha * m2 * m2 + beta * snr_y2;
+            }
+            const float y1_2 = snr_y1 * snr_y1, sig = std::sqrt(std::max(0.0f, 2 * y1_2 - snr_y2)), noise = snr_y1 - sig;
+            const float v = (sig > 0 && noise > 0) ? std::max(0.0f, 10.0f * std::log10(sig / noise)) : 0.0f;
+            snr = v;
+            if (v > peak_snr)
+                peak_snr = v;
+        }
+
+    public:
+        RealDemodHipModule(std::string input_file, std::string output_file_hint, nlohmann::json parameters) : ProcessingModule(input_file, output_file_hint, parameters)
+        {
+            sdhip_fsk_cfg_default(KIND, &cfg, &ext);
+            // BaseDemodModule ctor (module_demod_base.cpp:12-57) + the module's own (module_fsk_demod.cpp:12-57, module_sdpsk_demod.cpp:13-55)
+            parse_base_demod(parameters, cfg, who());
+            if (KIND == SDHIP_REAL_FSK)
+            {
+                bool b = false;
+                opt(parameters, "basic_shaping", b), ext.basic_shaping = b;
+            }
+            if (parameters.count("rrc_alpha") > 0)
+                cfg.rrc_alpha = parameters["rrc_alpha"].get<float>();
+            else if (!ext.basic_shaping)
+                throw satdump_exception("RRC Alpha parameter must be present!");
+            opt(parameters, "rrc_taps", cfg.rrc_taps);
+            if (parameters.count("clock_alpha") > 0)
+            {
+                const float clock_alpha = parameters["clock_alpha"].get<float>();
+                cfg.clock_gain_omega = pow(clock_alpha, 2) / 4.0;
+                cfg.clock_gain_mu = clock_alpha;
+            }
+            opt(parameters, "clock_gain_omega", cfg.clock_gain_omega);
+            opt(parameters, "clock_mu", cfg.clock_mu);
+            opt(parameters, "clock_gain_mu", cfg.clock_gain_mu);
+            opt(parameters, "clock_omega_relative_limit", cfg.clock_omega_relative_limit);
+            opt(parameters, "baseband_format", baseband_format);
+            opt(parameters, "hip_device", cfg.device);
+            opt(parameters, "hip_exact", cfg.exact);
+            fmt = baseband_format == "ziq" ? SDHIP_FMT_CF32 : baseband_fmt_of(baseband_format, who());
+        }
+        ~RealDemodHipModule()
+        {
+            if (h)
+                sdhip_demod_destroy(h);
+        }
+        // Can the HIP path run this parameter set? The override keeps the CPU module otherwise.
+        static bool covers(const std::string &input_file, const std::string &output_file_hint, const nlohmann::json &parameters, std::string &why)
+        {
+            if (parameters.count("enable_doppler") > 0 && parameters["enable_doppler"].get<bool>())
+            {
+                why = "enable_doppler";
+                return false;
+            }
+            try
+            {
+                RealDemodHipModule probe(input_file, output_file_hint, parameters);
+                if (probe.baseband_format == "ziq" && std::filesystem::exists(input_file))
+                    BasebandFile probe_file(input_file, probe.baseband_format, probe.fmt, who());
+                void *e = sdhip_fsk_demod_create(&probe.cfg, &probe.ext);
+                if (!e)
+                {
+                    why = sdhip_last_error();
+                    return false;
+                }
+                sdhip_demod_destroy(e);
+                return true;
+            }
+            catch (const std::exception &ex)
+            {
+                why = ex.what();
+                return false;
+            }
+        }
+
+        std::vector<ModuleDataType> getInputTypes() { return {DATA_FILE, DATA_DSP_STREAM}; }
+        std::vector<ModuleDataType> getOutputTypes() { return {DATA_FILE, DATA_STREAM}; }
+
+        void init()
+        {
+            h = sdhip_fsk_demod_create(&cfg, &ext);
+            if (!h)
+                throw satdump_exception(std::string(who()) + ": " + sdhip_last_error());
+        }
+        void stop() { should_stop = true; }
+
+        void drain(std::vector<int8_t> &buf)
+        {
+            for (;;)
+            {
+                const int64_t n = sdhip_demod_pull(h, buf.data(), buf.size());
+                if (n < 0)
+                    throw satdump_exception(std::string(who()) + ": " + sdhip_last_error());
+                if (n == 0)
+                    break;
+                if (output_data_type == DATA_FILE)
+                    data_out.write((char *)buf.data(), n);
+                else
+                    output_fifo->write((uint8_t *)buf.data(), n);
+                snr_update(buf.data(), (size_t)n);
+            }
+        }
+
+        void process()
+        {
+            if (output_data_type == DATA_FILE)
+            {
+                data_out = std::ofstream(d_output_file_hint + ".soft", std::ios::binary);
+                d_output_file = d_output_file_hint + ".soft";
+            }
+            logger->info("Using input baseband " + d_input_file);
+            logger->info("Demodulating to " + d_output_file_hint + ".soft (MI355X path)");
+            if (baseband_format == "ziq" && input_data_type == DATA_FILE)
+                fmt = ziq_fmt_of(ziq_header_of(d_input_file), who()); // the sample format is the file's own (ziq.cpp:116-126)
+            std::vector<int8_t> out(1 << 24);
+            static const int bps[5] = {8, 4, 2, 2, 8}; // bytes per complex sample, indexed by SDHIP_FMT_*
+            if (input_data_type == DATA_FILE)
+            {
+                BasebandFile in(d_input_file, baseband_format, fmt, who()); // wav / RF64 / ZIQ header skipped, a ZIQ zstd stream undone
+                filesize = in.filesize;
+                progress = in.data_start;
+                const size_t samples_per_read = 1 << 22;
+                std::vector<char> raw(samples_per_read * bps[fmt]);
+                while (!should_stop)
+                {
+                    const size_t got = in.read(raw.data(), raw.size()) / bps[fmt];
+                    if (got == 0)
+                        break;
+                    if (sdhip_demod_push(h, raw.data(), got, fmt) < 0)
+                        throw satdump_exception(std::string(who()) + ": " + sdhip_last_error());
+                    progress = in.consumed();
+                    drain(out);
+                }
+            }
+            else
+            { // dsp::stream<complex_t> hand-off; everything pending is processed as soon as an eighth of a second of samples has arrived (see psk_demod_hip)
+                const size_t flush_every = std::max<size_t>(8192, (size_t)(cfg.samplerate / 8.0));
+                size_t since_flush = 0;
+                while (!should_stop && input_active.load())
+                {
+                    const int n = input_stream->read();
+                    if (n <= 0)
+                        continue;
+                    const int rc = sdhip_demod_push(h, input_stream->readBuf, (size_t)n, SDHIP_FMT_CF32);
+                    input_stream->flush();
+                    if (rc < 0)
+                        throw satdump_exception(std::string(who()) + ": " + sdhip_last_error());
+                    since_flush += (size_t)n;
+                    if (since_flush >= flush_every)
+                    {
+                        if (sdhip_demod_flush(h) < 0)
+                            throw satdump_exception(std::string(who()) + ": " + sdhip_last_error());
+                        since_flush = 0;
+                    }
+                    drain(out);
+                }
+            }
+            if (sdhip_demod_flush(h) < 0)
+                throw satdump_exception(std::string(who()) + ": " + sdhip_last_error());
+            drain(out);
+            if (output_data_type == DATA_FILE)
+                data_out.close();
+            logger->info("Demodulation finished");
+        }
+
+        void drawUI(bool) {}
+
+        nlohmann::json getModuleStats()
+        {
+            nlohmann::json v;
+            v["progress"] = filesize ? ((double)progress / (double)filesize) : 0.0;
+            v["snr"] = snr.load();
+            v["peak_snr"] = peak_snr.load();
+            return v;
+        }
+
+        static std::string getID() { return who(); }
+        virtual std::string getIDM() { return getID(); }
+        static nlohmann::json getParams()
+        { // the advertised defaults of FSKDemodModule::getParams / SDPSKDemodModule::getParams
+            nlohmann::json v;
+            v["rrc_alpha"] = 0.5;
+            v["rrc_taps"] = 31;
+            return v;
+        }
+        static std::shared_ptr<ProcessingModule> getInstance(std::string input_file, std::string output_file_hint, nlohmann::json parameters)
+        {
+            return std::make_shared<RealDemodHipModule>(input_file, output_file_hint, parameters);
+        }
+    };
+    using FSKDemodHipModule = RealDemodHipModule<SDHIP_REAL_FSK>;
+    using SDPSKDemodHipModule = RealDemodHipModule<SDHIP_REAL_SDPSK>;
 
     // ------------------------------------------------------------------------------- concatenated decoders
     class FecHipModuleBase : public base::FileStreamToFileStreamModule
@@ -1937,6 +2158,8 @@ namespace sdhip_plugin
         static void registerModulesHandler(const RegisterModulesEvent &evt)
         {
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, PSKDemodHipModule);
+            REGISTER_MODULE_EXTERNAL(evt.modules_registry, FSKDemodHipModule);
+            REGISTER_MODULE_EXTERNAL(evt.modules_registry, SDPSKDemodHipModule);
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, CCSDSConvConcatDecoderHipModule);
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, MetOpAHRPTDecoderHipModule);
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, CCSDSSimplePSKDecoderHipModule);
@@ -1970,6 +2193,20 @@ namespace sdhip_plugin
                             return cpu(in, out, p);
                         }
                         return PSKDemodHipModule::getInstance(in, out, p);
+                    };
+                }
+                else if (e.id == "fsk_demod" || e.id == "sdpsk_demod")
+                { // the real-valued demodulators; parameter sets the handle refuses (Doppler correction, ...) stay on the CPU module
+                    auto cpu = e.inst;
+                    const bool fsk = e.id == "fsk_demod";
+                    e.inst = [cpu, fsk](std::string in, std::string out, nlohmann::json p) -> std::shared_ptr<ProcessingModule> {
+                        std::string why;
+                        if (!(fsk ? FSKDemodHipModule::covers(in, out, p, why) : SDPSKDemodHipModule::covers(in, out, p, why)))
+                        {
+                            logger->info(std::string("sdhip_support: ") + (fsk ? "fsk_demod" : "sdpsk_demod") + " stays on the CPU module for this run (" + why + ")");
+                            return cpu(in, out, p);
+                        }
+                        return fsk ? FSKDemodHipModule::getInstance(in, out, p) : SDPSKDemodHipModule::getInstance(in, out, p);
                     };
                 }
                 else if (e.id == "ccsds_conv_concat_decoder")

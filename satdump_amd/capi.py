@@ -19,6 +19,8 @@ RATE_1_2, RATE_2_3, RATE_3_4, RATE_5_6, RATE_7_8 = 0, 1, 2, 3, 4
 FMT_CF32, FMT_CS16, FMT_CS8, FMT_CU8, FMT_CS32 = 0, 1, 2, 3, 4
 DEC_CONV_CONCAT, DEC_METOP_AHRPT, DEC_SIMPLE_PSK, DEC_FENGYUN_AHRPT, DEC_FENGYUN_MPT = 0, 1, 2, 3, 4
 CONSTELLATIONS = {"bpsk": BPSK, "bpsk_90": BPSK_90, "qpsk": QPSK, "oqpsk": OQPSK, "8psk": PSK8}
+REAL_FSK, REAL_SDPSK = 0, 1
+REAL_KINDS = {"fsk": REAL_FSK, "sdpsk": REAL_SDPSK}
 
 
 class DemodCfg(C.Structure):
@@ -31,6 +33,10 @@ class DemodCfg(C.Structure):
         ("has_carrier", C.c_int), ("carrier_pll_bw", C.c_float), ("carrier_pll_max_offset", C.c_float), ("exact", C.c_int), ("chunk_len", C.c_int), ("warmup", C.c_int), ("device", C.c_int), ("freq_shift", C.c_double),
         ("doppler", C.c_int), ("doppler_alpha", C.c_float), ("custom_samplerate", C.c_double),
     ]
+
+
+class FskExt(C.Structure):
+    _fields_ = [("kind", C.c_int), ("basic_shaping", C.c_int)]
 
 
 class DemodStats(C.Structure):
@@ -172,6 +178,10 @@ def lib():
                 L.sdhip_demod_doppler_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
             L.sdhip_op_block.restype = C.c_int64
             L.sdhip_op_block.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        if hasattr(L, "sdhip_fsk_demod_create"):
+            L.sdhip_fsk_cfg_default.argtypes = [C.c_int, C.POINTER(DemodCfg), C.POINTER(FskExt)]
+            L.sdhip_fsk_demod_create.restype = C.c_void_p
+            L.sdhip_fsk_demod_create.argtypes = [C.POINTER(DemodCfg), C.POINTER(FskExt)]
         if hasattr(L, "sdhip_dvbs2_front_create"):
             L.sdhip_dvbs2_front_create.restype = C.c_void_p
             L.sdhip_dvbs2_front_create.argtypes = [C.POINTER(DemodCfg)]
@@ -427,6 +437,30 @@ class PskDemod:
         """The Doppler rotator's target frequencies (rad / sample) for the source buffers to come (sdhip_demod_doppler_targets)."""
         t = np.ascontiguousarray(targets, dtype=np.float32)
         _check(lib().sdhip_demod_doppler_targets(self.h, t.ctypes.data_as(C.c_void_p), len(t)), "sdhip_demod_doppler_targets")
+
+
+def fsk_cfg(kind: str | int = "fsk", **kw):
+    """(DemodCfg, FskExt) with the fsk_demod / sdpsk_demod MODULE's defaults (sdhip_fsk_cfg_default), then the keywords: DemodCfg's fields, or `basic_shaping`."""
+    c, x = DemodCfg(), FskExt()
+    lib().sdhip_fsk_cfg_default(REAL_KINDS[kind] if isinstance(kind, str) else int(kind), C.byref(c), C.byref(x))
+    for k, v in kw.items():
+        if k == "basic_shaping":
+            x.basic_shaping = int(bool(v))
+        else:
+            setattr(c, k, v)
+    return c, x
+
+
+class FskDemod(PskDemod):
+    """fsk_demod / sdpsk_demod on one GPU stream (sdhip_fsk_demod_create): PskDemod's methods on the handle; ONE int8 -- and with syms_ptr ONE float -- per symbol."""
+
+    def __init__(self, cfg, ext: FskExt | None = None):
+        if isinstance(cfg, tuple):
+            cfg, ext = cfg
+        self.cfg, self.ext = cfg, ext
+        self.h = lib().sdhip_fsk_demod_create(C.byref(cfg), C.byref(ext))
+        if not self.h:
+            raise SdhipError(f"sdhip_fsk_demod_create failed: {last_error()}")
 
 
 class LdpcDecoder:

@@ -2,6 +2,7 @@
 // module does it (module_demod_base.cpp:12-89, module_psk_demod.cpp:12-136), stage sequencing, the
 // boundary certificates of the chunk-speculative loop stages, stream-state carry, and the C ABI.
 #include "demod_kernels.h"
+#include "fsk_kernels.h"
 #include "dsp_design.h"
 namespace sdhip
 {
@@ -194,6 +195,20 @@ namespace sdhip
             return;
         const float m = fmaxf(fabsf(b.acc_re), fabsf(b.acc_im));
         if (fabsf(a.acc_re - b.acc_re) <= tol * m && fabsf(a.acc_im - b.acc_im) <= tol * m)
+            atomicAdd(&vo->inexact, 1);
+        else
+            verdict_fail(vo, fails, k, force);
+    }
+    // CorrectIQBlock<float> (acc_re alone): within tol |acc| + floor of the predecessor's end -- the floor for an accumulator that hovers about zero
+    __global__ void k_fdc_verdict(int K, const DcState *spec, const DcState *endst, float tol, float floor_abs, VerdictOut *vo, int *fails, int force)
+    {
+        const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+        if (k < 1 || k >= K)
+            return;
+        const float a = spec[k].acc_re, b = endst[k - 1].acc_re;
+        if (__float_as_uint(a) == __float_as_uint(b))
+            return;
+        if (fabsf(a - b) <= tol * fabsf(b) + floor_abs)
             atomicAdd(&vo->inexact, 1);
         else
             verdict_fail(vo, fails, k, force);
@@ -456,10 +471,26 @@ namespace sdhip
         int only = 0;
     };
 
+    // fsk_demod / sdpsk_demod (module_fsk_demod.cpp, module_sdpsk_demod.cpp) run on the same engine: everything up to and including BaseDemodModule's complex AGC is
+    // the PSK chain's, behind it the real-valued stages of fsk_kernels.h take over (DemodEngine::fsk_tail)
+    struct FskExt
+    {
+        bool on = false;
+        int kind = SDHIP_REAL_FSK; // SDHIP_REAL_FSK: the float AGC is there, scale 50; SDHIP_REAL_SDPSK: no float AGC, scale 400
+        int basic_shaping = 0;
+        // sdhip_op_block's unit entries: ONE real-valued block on its own (1 quadrature demodulator .. 5 clock recovery), constructed with the values below
+        int only = 0;
+        float q_gain = 1.0f;                           // QuadratureDemodBlock(gain)
+        float agc_rate = 0.1f, agc_ref = 0.5f, agc_gain = 1.0f, agc_max = 65535.0f; // AGCBlock<float>(...), module_fsk_demod.cpp:68
+        float omega = 0.0f;                            // > 0: MMClockRecoveryBlock<float>'s omega instead of final_sps
+        int box_taps = 0;                              // > 0: that many taps of 0.1f instead of the module's loop over final_sps
+    };
+
     struct DemodEngine
     {
         sdhip_demod_cfg cfg;
         NdspExt nd;
+        FskExt fsk;
         long long fir_drop = 0; // ndsp FIRBlock latency: the first ntaps outputs of the stream do not exist there (dsp/filter/fir.cpp:80-83)
         DevBuf<cf32> symtmp;    // ndsp: the clock recovery's symbols, input of the symbol-rate Costas loop
         hipStream_t stream = nullptr;
@@ -611,10 +642,18 @@ namespace sdhip
 
         static int fmt_bytes(int fmt) { return (fmt == SDHIP_FMT_CF32 || fmt == SDHIP_FMT_CS32) ? 8 : (fmt == SDHIP_FMT_CS16 ? 4 : 2); }
 
-        explicit DemodEngine(const sdhip_demod_cfg &c, const NdspExt *ne = nullptr) : cfg(c)
+        explicit DemodEngine(const sdhip_demod_cfg &c, const NdspExt *ne = nullptr, const FskExt *fe = nullptr) : cfg(c)
         {
             if (ne)
                 nd = *ne;
+            if (fe)
+            { // constellation, pll_bw, has_carrier and post_costas_dc are not the real-valued modules' keys: not read
+                fsk = *fe;
+                cfg.constellation = SDHIP_BPSK;
+                cfg.has_carrier = 0;
+                cfg.post_costas_dc = 0;
+                cfg.pll_bw = 0.0f;
+            }
             SD_HIP(hipSetDevice(cfg.device));
             SD_HIP(hipStreamCreate(&stream));
             if (cfg.samplerate <= 0)
@@ -736,8 +775,22 @@ namespace sdhip
             agc_s.gain = agc_p.init_gain;
             // RRC (module_psk_demod.cpp:91)
             // ndsp: RRC_Block::set_cfg designs from its double members (dsp/filter/rrc.h:62-66)
-            std::vector<float> rrc = nd.on ? design::rrc(nd.rrc_gain, nd.samplerate, nd.symbolrate, nd.rrc_alpha, cfg.rrc_taps)
-                                           : design::rrc(1, final_samplerate, d_symbolrate, cfg.rrc_alpha, cfg.rrc_taps);
+            std::vector<float> rrc;
+            if (fsk.on && (fsk.basic_shaping || fsk.box_taps > 0))
+            { // module_fsk_demod.cpp:72-77: `for (int i = 0; i < final_sps; i++)` with the float final_sps -- 2.55 gives three taps
+                if (fsk.box_taps > 0)
+                    rrc.assign((size_t)fsk.box_taps, 0.1f);
+                else
+                    for (int i = 0; i < final_sps; i++)
+                        rrc.push_back(0.1f);
+            }
+            else
+            {
+                if (fsk.on && !(cfg.rrc_alpha > 0))
+                    throw HipError("RRC Alpha parameter must be present!");
+                rrc = nd.on ? design::rrc(nd.rrc_gain, nd.samplerate, nd.symbolrate, nd.rrc_alpha, cfg.rrc_taps)
+                            : design::rrc(1, final_samplerate, d_symbolrate, cfg.rrc_alpha, cfg.rrc_taps);
+            }
             rrc_ntaps = (int)rrc.size();
             if (rrc_ntaps > DEMOD_HIST || rrc_ntaps > 384)
                 throw HipError("rrc_taps too large for the HIP path");
@@ -747,7 +800,7 @@ namespace sdhip
             d_rrc.reserve(rrev.size());
             SD_HIP(hipMemcpy(d_rrc.p, rrev.data(), rrev.size() * sizeof(float), hipMemcpyHostToDevice));
             // the 31-tap filter every pipeline of the path uses rides on the AGC lanes (SDHIP_FUSE_AGC_FIR=0: two kernels, A/B switch)
-            fuse_agc_fir = rrc_ntaps == AGCFIR_NT && env_int("SDHIP_FUSE_AGC_FIR", 1) != 0 && !nd.on; // ndsp filters BEFORE the AGC
+            fuse_agc_fir = rrc_ntaps == AGCFIR_NT && env_int("SDHIP_FUSE_AGC_FIR", 1) != 0 && !nd.on && !fsk.on; // ndsp filters BEFORE the AGC; fsk / sdpsk filter a REAL stream
             fir_drop = nd.on ? rrc_ntaps : 0;
             if (fuse_agc_fir)
             {
@@ -870,6 +923,8 @@ namespace sdhip
                 rot_mag_eps = (float)(std::sqrt((double)rot_dre * rot_dre + (double)rot_dim * rot_dim) - 1.0);
                 d_rot_state.reserve(1);
             }
+            if (fsk.on)
+                fsk_init();
             stats.final_sps = final_sps;
             stats.final_samplerate = final_samplerate;
             stats.buffer_size = d_buffer_size;
@@ -2511,6 +2566,16 @@ namespace sdhip
             }
             tick("resample");
 
+            if (fsk.on)
+            { // fsk_demod / sdpsk_demod: BaseDemodModule's complex AGC (module_demod_base.cpp:207), then the real-valued chain
+                const cf32 *AIN = (in_place && !resample) ? SRC : A;
+                agc_stage(AIN, B, n);
+                tick("agc");
+                const int64_t nsoft = fsk_tail(B, n, d_soft, soft_cap, d_syms, syms_cap);
+                tick("real chain");
+                started = true;
+                return nsoft;
+            }
             ChunkGeom cg;
             if (fuse_afc)
             {
@@ -2734,6 +2799,298 @@ namespace sdhip
             SD_HIP(hipStreamSynchronize(stream));
             started = true;
             return nsym;
+        }
+
+        // ==== fsk_demod / sdpsk_demod: the real-valued chain behind the complex AGC (fsk_kernels.h) ====================================================
+        // Stream state: the quadrature demodulator's last angle (on the device, two words used in turn), the DC block's accumulator, the float AGC's gain,
+        // the FIR's and the clock recovery's input history (on the device), the clock recovery's loop state.
+        DevBuf<float> d_fq, d_fh_fir, d_fh_mm, d_ftaps, fbufA, fbufB, d_frows;
+        int fq_sel = 0, f_ntaps = 0;
+        DcState fdc_s{0.0f, 0.0f};
+        AgcState fagc_s{1.0f};
+        FagcParams fagc_p{};
+        FmmParams fmm_p{};
+        FmmState fmm_s{};
+        DevBuf<FmmState> d_fmm_start, d_fmm_spec, d_fmm_end;
+        DevBuf<AgcState> d_fagc_start;
+        long long w_fmm_learned = 0;
+        double fmm_level = 0.5; // mean |x| of the clock recovery's input, measured over the head of every call of 4096 samples or more
+        void fsk_init()
+        {
+            d_fq.reserve(2);
+            d_fh_fir.reserve(FSK_HIST);
+            d_fh_mm.reserve(FSK_HIST);
+            SD_HIP(hipMemset(d_fq.p, 0, 2 * sizeof(float))); // QuadratureDemodBlock::phase = 0 (quadrature_demod.h:17)
+            SD_HIP(hipMemset(d_fh_fir.p, 0, FSK_HIST * sizeof(float)));
+            SD_HIP(hipMemset(d_fh_mm.p, 0, FSK_HIST * sizeof(float)));
+            // the filter's taps: the constructor designed them (RRC, or basic_shaping's run of 0.1f) and holds them reversed in d_rrc
+            f_ntaps = rrc_ntaps;
+            fagc_p = FagcParams{fsk.agc_rate, fsk.agc_ref, fsk.agc_max, fsk.agc_gain};
+            fagc_s.gain = fsk.agc_gain;
+            d_fagc_start.reserve(1);
+            const float omega = fsk.omega > 0 ? fsk.omega : final_sps;
+            fmm_p.omega_gain = cfg.clock_gain_omega;
+            fmm_p.mu_gain = cfg.clock_gain_mu;
+            fmm_p.omega_mid = omega;
+            fmm_p.omega_limit = cfg.clock_omega_relative_limit * omega; // clock_recovery_mm.cpp:15
+            fmm_p.init_mu = cfg.clock_mu;
+            fmm_p.bank = d_mmbank.p;
+            // the rows hold one symbol per input sample at most
+            if (!((double)omega * (1.0 - std::fabs((double)cfg.clock_omega_relative_limit)) >= 0.99))
+                throw HipError("fsk / sdpsk demod: fewer than one sample per symbol");
+            fmm_s.mu = cfg.clock_mu;
+            fmm_s.omega = omega;
+            fmm_s.last = 0.0f; // (`last_sample` has no initialiser in the reference: taken as zero, as the fixtures' driver pins it)
+            fmm_s.pad = 0;
+            fmm_s.inc = 0;
+            d_fmm_start.reserve(1);
+        }
+        void fsk_quad(const cf32 *in, float *out, long long n)
+        {
+            launch_fquad(in, out, n, fsk.q_gain, d_fq.p + fq_sel, d_fq.p + (fq_sel ^ 1), stream);
+            fq_sel ^= 1;
+        }
+        // CorrectIQBlock<float>: the complex DC block's scheme on floats -- chunk start values by the affine scan in double, a lane per chunk running the float
+        // recurrence, the boundary certified within 1e-5 |acc| (+ 1e-7: the accumulator of a stream without offset hovers about zero)
+        void fsk_dc(const float *in, float *out, long long n)
+        {
+            const int L = pick_L(n, ST_AGC);
+            const ChunkGeom g = make_geom(n, L, 0);
+            d_dc_spec.reserve(g.K);
+            d_dc_end.reserve(g.K);
+            d_dc_starts.reserve(g.K);
+            std::vector<DcState> starts((size_t)g.K);
+            if (g.K > 1)
+            {
+                d_dc_partial.reserve((size_t)g.K);
+                launch_fdc_partial(in, g, d_dc_partial.p, stream);
+                std::vector<double> part((size_t)g.K);
+                SD_HIP(hipMemcpyAsync(part.data(), d_dc_partial.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+                SD_HIP(hipStreamSynchronize(stream));
+                const double beta = (double)(1.0f - 0.0001f);
+                double a = fdc_s.acc_re;
+                for (int k = 0; k < g.K; k++)
+                {
+                    starts[k] = DcState{(float)a, 0.0f};
+                    a = std::pow(beta, (double)(chunk_end(g, k) - chunk_begin(g, k))) * a + part[(size_t)k];
+                }
+            }
+            starts[0] = fdc_s;
+            SD_HIP(hipMemcpyAsync(d_dc_starts.p, starts.data(), starts.size() * sizeof(DcState), hipMemcpyHostToDevice, stream));
+            launch_fdc(in, out, g, d_dc_starts.p, d_dc_spec.p, d_dc_end.p, nullptr, 0, stream);
+            verify_fix(
+                "fdc", g.K,
+                [&](VerdictOut *vo, int *fails, int force) {
+                    hipLaunchKernelGGL(k_fdc_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_dc_spec.p, d_dc_end.p, 1e-5f, 1e-7f, vo, fails, force);
+                },
+                [&](const int *list, int nr) {
+                    hipLaunchKernelGGL(k_spec_from_prev<DcState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_dc_spec.p, d_dc_end.p);
+                },
+                [&](const int *redo, int nr) { launch_fdc(in, out, g, d_dc_starts.p, d_dc_spec.p, d_dc_end.p, redo, nr, stream); });
+            stats.chunks += g.K;
+            SD_HIP(hipMemcpyAsync(&fdc_s, d_dc_end.p + (g.K - 1), sizeof(fdc_s), hipMemcpyDeviceToHost, stream));
+            SD_HIP(hipStreamSynchronize(stream)); // (starts is a local)
+        }
+        // AGCBlock<float>(0.1, 0.5, 1, 65535): a lane per chunk warming up from gain 1. The gain's map per sample is g <- (1 - rate |x|) g + rate reference: at
+        // rate 0.1 and a settled gain G it contracts by (1 - 0.05 / G) a sample, so 24 G / rate samples bring any start gain to the float floor.
+        void fsk_agc(const float *in, float *out, long long n)
+        {
+            const int L = pick_L(n, ST_AGC);
+            const double tau = std::max(1.0f, fagc_s.gain) / std::max(1e-6f, fagc_p.rate);
+            long long W = cfg.exact ? 0 : (cfg.warmup > 0 ? cfg.warmup : (long long)(24.0 * tau));
+            W = (std::min<long long>(std::max<long long>(W, cfg.exact ? 0 : 256), 1 << 20) + 255) / 256 * 256;
+            const ChunkGeom g = make_geom(n, L, (int)W);
+            d_agc_spec.reserve(g.K);
+            d_agc_end.reserve(g.K);
+            SD_HIP(hipMemcpyAsync(d_fagc_start.p, &fagc_s, sizeof(fagc_s), hipMemcpyHostToDevice, stream));
+            launch_fagc(in, out, g, fagc_p, d_fagc_start.p, d_agc_spec.p, d_agc_end.p, nullptr, 0, stream);
+            verify_fix(
+                "fagc", g.K,
+                [&](VerdictOut *vo, int *fails, int force) {
+                    hipLaunchKernelGGL(k_agc_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_agc_spec.p, d_agc_end.p, 1e-6f, vo, fails, force);
+                },
+                [&](const int *list, int nr) {
+                    hipLaunchKernelGGL(k_spec_from_prev<AgcState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_agc_spec.p, d_agc_end.p);
+                },
+                [&](const int *redo, int nr) { launch_fagc(in, out, g, fagc_p, d_fagc_start.p, d_agc_spec.p, d_agc_end.p, redo, nr, stream); });
+            stats.chunks += g.K;
+            SD_HIP(hipMemcpyAsync(&fagc_s, d_agc_end.p + (g.K - 1), sizeof(fagc_s), hipMemcpyDeviceToHost, stream));
+            SD_HIP(hipStreamSynchronize(stream));
+        }
+        // FIRBlock<float>: cur has FSK_HIST floats of room in front of it for the history
+        void fsk_fir(float *cur, float *out, long long n)
+        {
+            SD_HIP(hipMemcpyAsync(cur - FSK_HIST, d_fh_fir.p, FSK_HIST * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            launch_ffir(cur, out, n, d_rrc.p, f_ntaps, stream);
+            launch_fhist_slide(d_fh_fir.p, cur, n, stream);
+        }
+        // MMClockRecoveryBlock<float> + the module's quantiser: the complex stage's schedule (mm_stage) on the float loop -- a lane per chunk with a gear-shifted
+        // warm-up, the hand-off certified in time and rate by k_mm_verdict (MmCert: mu, omega, inc; `last_sample` follows from the data and the timing), failed
+        // lanes re-run from the predecessor's end state, the rows compacted into the stream by the chunk scan. Returns the symbols written.
+        int64_t fsk_mm(float *cur, long long n, float scale, int8_t *d_soft, size_t soft_cap, float *d_syms, size_t syms_cap)
+        {
+            SD_HIP(hipMemcpyAsync(cur - FSK_HIST, d_fh_mm.p, FSK_HIST * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            const float sps = fmm_p.omega_mid;
+            // The loop's time constant is 1 / (gain_mu x detector gain) symbols, and this detector's gain -- sign(last) * s - sign(s) * last -- goes with the LEVEL of
+            // the filtered stream: 0.43 (mean |x|) behind the float AGC and an RRC filter, 0.16 behind basic_shaping's run of 0.1f taps, where the complex chain's
+            // symbols have level 1. So the complex stage's warm-up lengths (mm_stage: 2.75 / gain_mu symbols in the fast gear + 16 / gain_mu to settle, 36 / gain_mu
+            // without the gear, doubled up to 64 / gain_mu while boundaries miss the tight window) are taken per unit of level: measured on the host twin, case B of
+            // tests/golden/fsk (level 0.16, gain_mu 1.7e-2) has boundaries outside the window behind 8 192 symbols of warm-up and none behind 16 384.
+            if (!cfg.exact && n >= 4096)
+            {
+                const long long m = std::min<long long>(n, 1 << 16);
+                launch_fmean_abs(cur, m, d_partial.p, stream);
+                double part[64];
+                SD_HIP(hipMemcpyAsync(part, d_partial.p, sizeof(part), hipMemcpyDeviceToHost, stream));
+                SD_HIP(hipStreamSynchronize(stream));
+                double sm = 0;
+                for (double v : part)
+                    sm += v;
+                if (std::isfinite(sm))
+                    fmm_level = std::min(1.0, std::max(0.05, sm / (double)m));
+            }
+            const double gmu = std::max(1e-4f, cfg.clock_gain_mu) * fmm_level;
+            fmm_p.fast_mult = 8.0f;
+            fmm_p.fast_syms = (int)(2.75 / gmu);
+            int L = pick_L(n, ST_MM);
+            const double w_full = 36.0 / gmu * sps, w_gear = (fmm_p.fast_syms + 16.0 / gmu) * sps;
+            const long long w_cap = (long long)(64.0 / gmu * sps);
+            long long W = cfg.exact ? 0 : (cfg.warmup > 0 ? cfg.warmup : (long long)std::min(w_full, std::max(w_gear, 0.5 * L)));
+            W = std::max(W, cfg.exact ? 0 : w_fmm_learned);
+            W = (W + 255) / 256 * 256;
+            // every lane runs W + L samples in sequence: with the chunk length left to the engine a chunk is at least half the warm-up (the lanes' work stays under 3 n)
+            if (!cfg.exact && cfg.chunk_len <= 0 && !getenv("SDHIP_CHUNK") && !getenv("SDHIP_CHUNK_MM"))
+                L = (int)std::min<long long>(std::max<long long>(L, (W / 2 + 63) / 64 * 64), 1 << 22);
+            // Hand-off windows, samples of timing (SDHIP_FMM_TIGHT_MICRO / SDHIP_FMM_TOL_MICRO: experiments). TIGHT is the complex stage's (mm_stage). Its re-run window of
+            // 5e-3 rests on a loop that is back on the floor a few hundred symbols into a chunk of thousands; this loop's time constant is 1 / level times as long
+            // -- longer than a chunk --, so a boundary outside the tight window is re-run from the predecessor's exact state.
+            const double TOL_TIGHT = env_int("SDHIP_FMM_TIGHT_MICRO", 200) * 1e-6, TOL = env_int("SDHIP_FMM_TOL_MICRO", 200) * 1e-6;
+            const float TOL_OMEGA = 1e-3f * sps;
+            ChunkGeom g;
+            auto setup = [&](long long Wn) {
+                g = make_geom(n, L, (int)Wn);
+                const double omin = (double)fmm_p.omega_mid - std::fabs((double)fmm_p.omega_limit);
+                const long long span0 = std::min<long long>(n, (long long)L + Wn);
+                fmm_p.cap = ((int)(span0 / std::max(0.5, omin - 0.01)) + 16 + 7) & ~7;
+                d_frows.reserve((size_t)g.K * fmm_p.cap);
+                d_counts.reserve(2 * (size_t)g.K);
+                d_offsets.reserve(g.K);
+                d_fmm_spec.reserve(g.K);
+                d_fmm_end.reserve(g.K);
+                d_mm_spec_c.reserve(g.K);
+                d_mm_end_c.reserve(g.K);
+                d_skip.reserve(g.K);
+                d_extra.reserve(g.K);
+                d_seg.reserve(2 * (size_t)g.K);
+            };
+            setup(W);
+            SD_HIP(hipMemcpyAsync(d_fmm_start.p, &fmm_s, sizeof(fmm_s), hipMemcpyHostToDevice, stream));
+            auto launch = [&](const int *redo, int nr) {
+                launch_fmm(cur, d_frows.p, d_counts.p, g, fmm_p, d_fmm_start.p, d_fmm_spec.p, d_fmm_end.p, d_mm_spec_c.p, d_mm_end_c.p, redo, nr, stream);
+            };
+            launch(nullptr, 0);
+            verify_fix(
+                "fmm", g.K,
+                [&](VerdictOut *vo, int *fails, int force) {
+                    hipLaunchKernelGGL(k_mm_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_mm_spec_c.p, d_mm_end_c.p, d_counts.p, TOL, TOL_TIGHT, TOL_OMEGA, d_skip.p,
+                                       d_extra.p, vo, fails, force);
+                },
+                [&](const int *list, int nr) {
+                    hipLaunchKernelGGL(k_spec_from_prev<MmCert>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_mm_spec_c.p, d_mm_end_c.p);
+                    hipLaunchKernelGGL(k_spec_from_prev<FmmState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_fmm_spec.p, d_fmm_end.p);
+                },
+                launch,
+                [&](int) { // many boundaries outside the tight window: the warm-up was too short for this signal's detector gain -- twice as long, and the stream keeps it
+                    const long long wn = (std::min<long long>(2 * (long long)g.W, w_cap) + 255) / 256 * 256;
+                    if (cfg.warmup > 0 || wn <= (long long)g.W)
+                        return false;
+                    w_fmm_learned = wn;
+                    setup(wn);
+                    launch(nullptr, 0);
+                    return true;
+                });
+            stats.chunks += g.K;
+            SD_HIP(hipMemsetAsync(d_vout.p, 0, sizeof(VerdictOut), stream));
+            {
+                const int nt = (g.K + 1023) / 1024;
+                d_tile_sums.reserve(nt);
+                hipLaunchKernelGGL(k_chunk_scan_sums, dim3(nt), dim3(1024), 0, stream, g.K, 1, nullptr, d_counts.p, d_skip.p, d_extra.p, fmm_p.cap, d_tile_sums.p, d_vout.p);
+                hipLaunchKernelGGL(k_chunk_scan_apply, dim3(nt), dim3(1024), 0, stream, g.K, 1, nullptr, 1, nullptr, d_counts.p, d_skip.p, d_extra.p, d_tile_sums.p, d_seg.p,
+                                   d_offsets.p, d_vout.p);
+            }
+            SD_HIP(hipMemcpyAsync(h_vout.p, d_vout.p, sizeof(VerdictOut), hipMemcpyDeviceToHost, stream));
+            SD_HIP(hipMemcpyAsync(&fmm_s, d_fmm_end.p + (g.K - 1), sizeof(fmm_s), hipMemcpyDeviceToHost, stream));
+            SD_HIP(hipStreamSynchronize(stream));
+            fmm_s.inc -= n; // clock_recovery_mm.cpp:123-126
+            if (fmm_s.inc < 0)
+                fmm_s.inc = 0;
+            if (h_vout.p->overflow)
+                throw HipError("symbol scratch overflow");
+            const long long tot = h_vout.p->total;
+            if ((size_t)tot > soft_cap)
+                throw HipError("soft output buffer too small");
+            if (d_syms && (size_t)tot > syms_cap)
+                throw HipError("symbol output buffer too small");
+            launch_fquant(d_frows.p, d_seg.p, d_offsets.p, g.K, fmm_p.cap, scale, d_soft, (long long)soft_cap, d_syms, (long long)syms_cap, stream);
+            launch_fhist_slide(d_fh_mm.p, cur, n, stream);
+            SD_HIP(hipStreamSynchronize(stream));
+            stats.symbols_out += tot;
+            last_symbols = tot;
+            return tot;
+        }
+        float *fsk_buf(DevBuf<float> &b, long long n)
+        {
+            b.reserve((size_t)n + FSK_HIST + 64);
+            return b.p + FSK_HIST;
+        }
+        // in: the complex AGC's output. ONE int8 per symbol to d_soft (clamp(sym * 50) fsk, clamp(sym * 400) sdpsk: module_fsk_demod.cpp:133-134,
+        // module_sdpsk_demod.cpp:119-120), ONE float per symbol to d_syms if asked for.
+        int64_t fsk_tail(const cf32 *in, long long n, int8_t *d_soft, size_t soft_cap, float *d_syms, size_t syms_cap)
+        {
+            float *F1 = fsk_buf(fbufA, n), *F2 = fsk_buf(fbufB, n);
+            fsk_quad(in, F1, n);
+            fsk_dc(F1, F2, n);
+            float *cur = F2, *oth = F1;
+            if (fsk.kind == SDHIP_REAL_FSK)
+            {
+                fsk_agc(cur, oth, n);
+                std::swap(cur, oth);
+            }
+            fsk_fir(cur, oth, n);
+            std::swap(cur, oth);
+            return fsk_mm(cur, n, fsk.kind == SDHIP_REAL_FSK ? 50.0f : 400.0f, d_soft, soft_cap, d_syms, syms_cap);
+        }
+        // sdhip_op_block's unit entries: ONE block (fsk.only) over the next n samples of its stream. d_in: complex floats for the quadrature demodulator,
+        // floats for the others; d_out: floats. Returns the samples (symbols) written.
+        int64_t fsk_block(const float *d_in, long long n, float *d_out, size_t out_cap)
+        {
+            SD_HIP(hipSetDevice(cfg.device));
+            if (n <= 0)
+                return 0;
+            if (fsk.only != 5 && out_cap < (size_t)n)
+                throw HipError("output too small");
+            float *F1 = fsk_buf(fbufA, 2 * n), *F2 = fsk_buf(fbufB, n);
+            SD_HIP(hipMemcpyAsync(F1, d_in, (size_t)n * (fsk.only == 1 ? sizeof(cf32) : sizeof(float)), hipMemcpyDeviceToDevice, stream));
+            int64_t nout = n;
+            if (fsk.only == 1)
+                fsk_quad(reinterpret_cast<const cf32 *>(F1), F2, n);
+            else if (fsk.only == 2)
+                fsk_dc(F1, F2, n);
+            else if (fsk.only == 3)
+                fsk_agc(F1, F2, n);
+            else if (fsk.only == 4)
+                fsk_fir(F1, F2, n);
+            else if (fsk.only == 5)
+            {
+                d_soft_tmp.reserve((size_t)n + 64);
+                nout = fsk_mm(F1, n, 1.0f, d_soft_tmp.p, (size_t)n + 64, d_out, out_cap);
+            }
+            else
+                throw HipError("unknown real-valued block");
+            if (fsk.only != 5)
+                SD_HIP(hipMemcpyAsync(d_out, F2, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            SD_HIP(hipStreamSynchronize(stream));
+            return nout;
         }
 
         // ---- host path
@@ -2983,6 +3340,40 @@ extern "C"
         return new DemodEngine(*cfg, &e);
         SD_GUARD_END(nullptr)
     }
+    // ---- fsk_demod / sdpsk_demod on the same engine
+    void sdhip_fsk_cfg_default(int kind, sdhip_demod_cfg *c, sdhip_fsk_ext *ext)
+    {
+        sdhip_demod_cfg_default(c); // BaseDemodModule's keys (agc_rate 1e-2, MIN_SPS / MAX_SPS 1.1 / 4.0, module_demod_base.h:54,71-72)
+        c->constellation = SDHIP_BPSK; // (not read)
+        c->clock_gain_omega = (float)(pow(1.7e-2, 2) / 4.0); // module_fsk_demod.h:28-31, module_sdpsk_demod.h:26-29
+        c->clock_mu = 0.5f;
+        c->clock_gain_mu = (float)1.7e-2;
+        c->clock_omega_relative_limit = 0.005f;
+        c->rrc_taps = 31;
+        if (kind == SDHIP_REAL_SDPSK)
+        { // module_sdpsk_demod.cpp:53-54
+            c->min_sps = 1.0f;
+            c->max_sps = 10.0f;
+        }
+        ext->kind = kind;
+        ext->basic_shaping = 0;
+    }
+    void *sdhip_fsk_demod_create(const sdhip_demod_cfg *cfg, const sdhip_fsk_ext *ext)
+    {
+        SD_GUARD_BEGIN
+        if (!cfg || !ext)
+            throw HipError("fsk / sdpsk demod: configuration missing");
+        if (ext->kind != SDHIP_REAL_FSK && ext->kind != SDHIP_REAL_SDPSK)
+            throw HipError("fsk / sdpsk demod: unknown kind");
+        if (ext->basic_shaping && ext->kind != SDHIP_REAL_FSK)
+            throw HipError("basic_shaping is fsk_demod's key");
+        FskExt e;
+        e.on = true;
+        e.kind = ext->kind;
+        e.basic_shaping = ext->basic_shaping ? 1 : 0;
+        return new DemodEngine(*cfg, nullptr, &e);
+        SD_GUARD_END(nullptr)
+    }
     int64_t sdhip_ndsp_psk_demod_work_dev(void *h, const float *d_in, size_t nsamples, float *d_out, size_t out_cap)
     {
         SD_GUARD_BEGIN
@@ -3085,6 +3476,57 @@ extern "C"
     {
         SD_GUARD_BEGIN
         SD_HIP(hipSetDevice(device));
+        if (kind >= 11 && kind <= 15)
+        { // the real-valued blocks of fsk_demod / sdpsk_demod, one exact lane each (include/sdhip.h). The LAST parameter says whether the call continues the
+          // stream of the previous call of that kind (the block's state is kept here until the next call that does not): a stream in several calls, as the
+          // reference's blocks see theirs in several buffers
+            static std::mutex mu;
+            static DemodEngine *streams[5]; // (never destroyed at exit: the runtime may be gone by then)
+            static const int nparams[5] = {1, 0, 4, 5, 5};
+            std::lock_guard<std::mutex> lk(mu);
+            DemodEngine *&e = streams[kind - 11];
+            const bool cont = params[nparams[kind - 11]] != 0.0f;
+            if (!cont || !e || e->cfg.device != device)
+            {
+                sdhip_demod_cfg c;
+                sdhip_fsk_ext x;
+                sdhip_fsk_cfg_default(SDHIP_REAL_FSK, &c, &x);
+                c.device = device;
+                c.exact = 1;
+                c.samplerate = 2.0e6; // (no resampler: two samples per symbol unless the filter's design says otherwise)
+                c.symbolrate = 1.0e6;
+                c.min_sps = 1.0f;
+                c.max_sps = 3.0e38f;
+                c.rrc_alpha = 0.5f;
+                FskExt f;
+                f.on = true;
+                f.only = kind - 10;
+                if (kind == 11)
+                    f.q_gain = params[0];
+                else if (kind == 13)
+                    f.agc_rate = params[0], f.agc_ref = params[1], f.agc_gain = params[2], f.agc_max = params[3];
+                else if (kind == 14)
+                {
+                    c.samplerate = params[0];
+                    c.symbolrate = params[1];
+                    c.rrc_alpha = params[2];
+                    c.rrc_taps = (int)params[3];
+                    f.box_taps = (int)params[4];
+                }
+                else if (kind == 15)
+                {
+                    f.omega = params[0];
+                    c.clock_gain_omega = params[1];
+                    c.clock_mu = params[2];
+                    c.clock_gain_mu = params[3];
+                    c.clock_omega_relative_limit = params[4];
+                }
+                delete e;
+                e = nullptr;
+                e = new DemodEngine(c, nullptr, &f);
+            }
+            return e->fsk_block(d_in, (long long)n, d_out, out_cap);
+        }
         const long long nn = (long long)n;
         DevBuf<cf32> in;
         in.reserve(n + 2 * DEMOD_HIST + 64);

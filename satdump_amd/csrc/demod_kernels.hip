@@ -6,6 +6,7 @@
 // precision with the same polynomial and reduction, so that a single sequential lane reproduces the
 // reference bit for bit (tests/test_demod_gpu.py, exact mode).
 #include "demod_kernels.h"
+#include "glibc_atan2f.h"
 #include <climits>
 #include <optional>
 #include <type_traits>
@@ -3575,3 +3576,7 @@ namespace sdhip
         hipLaunchKernelGGL(k_tail_copy, dim3((cnt + 63) / 64), dim3(64), 0, st, x, n, cnt, cg, rot, order, out);
     }
 } // namespace sdhip
+
+// the real-valued chain of fsk_demod / sdpsk_demod: its kernels and launch functions (they use this file's quantiser clamp and the shared arctangent)
+#define SDHIP_FSK_KERNELS_IMPL
+#include "fsk_kernels.h"

@@ -413,6 +413,58 @@ def to_cs16(x: np.ndarray) -> np.ndarray:
     return out
 
 
+def _erf(x: np.ndarray) -> np.ndarray:
+    """erf to 1.5e-7 (Abramowitz & Stegun 7.1.26): the Gaussian frequency pulse of modulate_fsk needs no more."""
+    x = np.asarray(x, dtype=np.float64)
+    t = 1.0 / (1.0 + 0.3275911 * np.abs(x))
+    y = 1.0 - (((((1.061405429 * t - 1.453152027) * t) + 1.421413741) * t - 0.284496736) * t + 0.254829592) * t * np.exp(-x * x)
+    return np.sign(x) * y
+
+
+def modulate_fsk(bits: np.ndarray, samplerate: float, symbolrate: float, h: float = 0.5, bt: float | None = None, esn0_db: float = 20.0, cfo_hz: float = 0.0,
+                 seed: int = 0, amplitude: float = 0.5, phase0: float = 0.3, noise: bool = True) -> np.ndarray:
+    """Continuous-phase 2-FSK at samplerate / symbolrate samples per symbol (any ratio): bit 1 = the upper tone, modulation index h (the phase moves
+    by +-pi h per symbol), the frequency pulse a rectangle of one symbol -- filtered by a Gaussian of bandwidth-time product `bt` when given (GFSK).
+    Constant envelope `amplitude`; Es/N0 counts the energy of one symbol's samples against the noise density, as in modulate(). Returns complex64.
+    What fsk_demod reads back: the quadrature demodulator's output is the phase step per sample, positive for a 1."""
+    a = np.asarray(bits, dtype=np.float64) * 2.0 - 1.0
+    nsym = len(a)
+    sps = float(samplerate) / float(symbolrate)
+    nout = int(nsym * sps)
+    t = (np.arange(nout, dtype=np.float64) + 0.5) / sps  # the middle of every sample interval, in symbols
+    k0 = np.floor(t).astype(np.int64)
+    if bt is None:
+        f = a[np.clip(k0, 0, nsym - 1)]  # frequency in units of pi h / symbol
+    else:
+        g = math.pi * float(bt) * math.sqrt(2.0 / math.log(2.0))
+        f = np.zeros(nout, dtype=np.float64)
+        for j in range(-3, 4):
+            k = k0 + j
+            d = t - (k + 0.5)  # distance from the middle of symbol k
+            q = 0.5 * (_erf(g * (d + 0.5)) - _erf(g * (d - 0.5)))
+            f += np.where((k >= 0) & (k < nsym), a[np.clip(k, 0, nsym - 1)], 0.0) * q
+    step = math.pi * h * f / sps  # phase step of every sample
+    m = np.arange(nout, dtype=np.float64)
+    ph = np.cumsum(step) + 2.0 * math.pi * (cfo_hz / float(samplerate)) * m + phase0
+    x = np.exp(1j * ph)
+    if noise:
+        rng = np.random.default_rng(seed + 7919)
+        sigma = math.sqrt(sps / (2.0 * 10 ** (esn0_db / 10)))
+        x = x + sigma * (rng.standard_normal(nout) + 1j * rng.standard_normal(nout))
+    return (x * amplitude).astype(np.complex64)
+
+
+def modulate_sdpsk(bits: np.ndarray, samplerate: float, symbolrate: float, rrc_alpha: float = 0.4, esn0_db: float = 20.0, cfo_hz: float = 0.0, seed: int = 0,
+                   amplitude: float = 0.5) -> np.ndarray:
+    """Symmetric differential PSK: the carrier phase moves by +90 degrees for a 1 and by -90 degrees for a 0 from symbol to symbol; RRC-shaped through
+    modulate(). What sdpsk_demod reads back: the phase steps per sample, summed over a symbol by its filter. Returns complex64."""
+    a = np.asarray(bits, dtype=np.float64) * 2.0 - 1.0
+    symbols = np.exp(1j * (math.pi / 2.0) * np.cumsum(a))
+    spec = SynthSpec(samplerate=samplerate, symbolrate=symbolrate, rrc_alpha=rrc_alpha, amplitude=amplitude, cfo_hz=cfo_hz, esn0_db=esn0_db, seed=seed)
+    x, _ = modulate(symbols, spec)
+    return x
+
+
 def soft_from_symbols(symbols: np.ndarray, spec: SynthSpec, sigma: float, seed: int, scale: float | None = None) -> np.ndarray:
     """Directly synthesise a .soft stream (int8) from symbols for FEC-only tests:
     BPSK 1 B/symbol (x50), QPSK 2 B/symbol (x100, unit-power symbols)."""
