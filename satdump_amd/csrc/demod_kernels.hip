@@ -883,7 +883,12 @@ namespace sdhip
     {
         float4 a, b, c, d;
     };
-    template <int D, bool FASTQ = false>
+    // Which magnitude the gain follows is an option of the launch, the same for every lane and every sample of it: a stage that names it (AGC_MAG_OUT /
+    // AGC_MAG_IN) holds that path alone, one that leaves it open (AGC_MAG_ARG) tests AgcParams::input_mag per sample as before.
+    constexpr int AGC_MAG_ARG = -1, // AgcParams::input_mag decides, per sample
+                  AGC_MAG_OUT = 0,  // AGCBlock (agc.cpp:25-39): |output sample|
+                  AGC_MAG_IN = 1;   // ndsp::AGCFastBlock (agc_fast.cpp:37-55): |input sample| times the gain
+    template <int D, bool FASTQ = false, int MAGQ = AGC_MAG_ARG>
     struct AgcStageT
     {
         using P = AgcParams;
@@ -893,15 +898,21 @@ namespace sdhip
         // early exit of a re-run lane (CKPT): is state a on the trajectory that left checkpoint b? (the AGC certificate's own rule)
         __device__ static __forceinline__ bool close(const S &a, const S &b, float tol_a, float) { return fabsf(a.gain - b.gain) <= tol_a * fabsf(b.gain); }
         __device__ static __forceinline__ void prewarm(S &, const P &, const cf32 *, long long) {}
-        __device__ static __forceinline__ cf32 step(S &s, const P &p, const cf32 v) { return step_t<FASTQ>(s, p, v); }
-        template <bool FAST>
+        __device__ static __forceinline__ cf32 step(S &s, const P &p, const cf32 v) { return step_t<FASTQ, MAGQ>(s, p, v); }
+        template <bool FAST, int MAG = AGC_MAG_ARG>
         __device__ static __forceinline__ cf32 step_t(S &s, const P &p, const cf32 v)
         {
+            static_assert(MAG == AGC_MAG_ARG || MAG == AGC_MAG_OUT || MAG == AGC_MAG_IN, "AGC_MAG_*");
+            bool input_mag;
+            if constexpr (MAG == AGC_MAG_ARG)
+                input_mag = p.input_mag != 0;
+            else
+                input_mag = MAG == AGC_MAG_IN;
             // AGCBlock<complex_t>::work, agc.cpp:25-39
             const float ore = v.re * s.gain;
             const float oim = v.im * s.gain;
             float mag;
-            if (p.input_mag)
+            if (input_mag)
             { // AGCFastBlock<complex_t>::process, agc_fast.cpp:37-55: mag_buf[i] = sqrtf(re * re + im * im) of the input (VOLK's generic kernel), times the gain
                 float mi;
                 if constexpr (FAST)
@@ -915,8 +926,12 @@ namespace sdhip
             else
                 mag = sqrtf(ore * ore + oim * oim) /* correctly rounded (default -fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn is the native approximation */;
             s.gain = s.gain + p.rate * (p.reference - mag);
-            if (p.max_gain > 0.0f && s.gain > p.max_gain)
-                s.gain = p.max_gain;
+            // the cap as ONE minimum against a bound that does not depend on the sample (max_gain, or +inf where there is none: the compiler forms it once, in
+            // front of the lane loop) instead of two comparisons and a select: for every gain that is not a NaN the value of
+            //     if (p.max_gain > 0.0f && s.gain > p.max_gain) s.gain = p.max_gain;
+            // bit for bit. A NaN gain (a NaN or an infinity in the input) leaves here as the bound where the reference keeps the NaN -- as in sd_clip_med3, the
+            // stream is lost either way.
+            s.gain = fminf(s.gain, p.max_gain > 0.0f ? p.max_gain : __builtin_inff());
             return cf32{ore, oim};
         }
     };
@@ -939,7 +954,7 @@ namespace sdhip
         asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(v));
         return r;
     }
-    template <bool FAST>
+    template <bool FAST, int MAG = AGC_MAG_ARG>
     struct AgcFirStageT
     {
         using P = AgcFirParams;
@@ -963,7 +978,7 @@ namespace sdhip
         __device__ static __forceinline__ v2f agc(S &s, const P &p, float re, float im)
         {
             AgcState a{s.gain};
-            const cf32 o = AgcStageT<4>::template step_t<FAST>(a, p.agc, cf32{re, im});
+            const cf32 o = AgcStageT<4>::template step_t<FAST, MAG>(a, p.agc, cf32{re, im});
             s.gain = a.gain;
             return v2f{o.re, o.im};
         }
@@ -1779,21 +1794,21 @@ namespace sdhip
     //   AfcFull<O> : AGC + filter + Costas
     // Arithmetic per stage = AgcFirStage / CostasStage, operation for operation (exact mode: bit for bit the reference).
     // =============================================================================================
-    template <bool FAST>
+    template <bool FAST, int MAG>
     struct AfcAgcOnly
     {
         using P = AfcParams;
         using S = AfcState;
         static constexpr int DEPTH = 4;
-        __device__ static __forceinline__ Blk8 block(S &s, const P &p, const Blk8 &c, bool) { return AgcFirStageT<FAST>::block(s.af, p.af, c, false); }
-        __device__ static __forceinline__ cf32 step(S &s, const P &p, const cf32 v) { return AgcFirStageT<FAST>::step(s.af, p.af, v); }
+        __device__ static __forceinline__ Blk8 block(S &s, const P &p, const Blk8 &c, bool) { return AgcFirStageT<FAST, MAG>::block(s.af, p.af, c, false); }
+        __device__ static __forceinline__ cf32 step(S &s, const P &p, const cf32 v) { return AgcFirStageT<FAST, MAG>::step(s.af, p.af, v); }
     };
     struct AfcEstState
     {
         AfcState s;
         float cr, ci, ar, ai, rc, rs; // exp(-j M f n) by recurrence, the running sum, the recurrence's step
     };
-    template <int M, bool FAST>
+    template <int M, bool FAST, int MAG>
     struct AfcEst
     {
         using P = AfcParams;
@@ -1816,7 +1831,7 @@ namespace sdhip
         }
         __device__ static __forceinline__ Blk8 block(S &e, const P &p, const Blk8 &c, bool)
         {
-            const Blk8 f = AgcFirStageT<FAST>::block(e.s.af, p.af, c, true);
+            const Blk8 f = AgcFirStageT<FAST, MAG>::block(e.s.af, p.af, c, true);
             acc(e, f.a.x, f.a.y);
             acc(e, f.a.z, f.a.w);
             acc(e, f.b.x, f.b.y);
@@ -1829,12 +1844,12 @@ namespace sdhip
         }
         __device__ static __forceinline__ cf32 step(S &e, const P &p, const cf32 v)
         {
-            const cf32 f = AgcFirStageT<FAST>::step(e.s.af, p.af, v);
+            const cf32 f = AgcFirStageT<FAST, MAG>::step(e.s.af, p.af, v);
             acc(e, f.re, f.im);
             return f;
         }
     };
-    template <int ORDER, bool FAST>
+    template <int ORDER, bool FAST, int MAG>
     struct AfcFull
     {
         using P = AfcParams;
@@ -1843,7 +1858,7 @@ namespace sdhip
         static constexpr int DEPTH = 4;
         __device__ static __forceinline__ Blk8 block(S &s, const P &p, const Blk8 &c, bool)
         {
-            const Blk8 f = AgcFirStageT<FAST>::block(s.af, p.af, c, true);
+            const Blk8 f = AgcFirStageT<FAST, MAG>::block(s.af, p.af, c, true);
             const cf32 a0 = Cos::step(s.cos, p.cos, cf32{f.a.x, f.a.y});
             const cf32 a1 = Cos::step(s.cos, p.cos, cf32{f.a.z, f.a.w});
             const cf32 a2 = Cos::step(s.cos, p.cos, cf32{f.b.x, f.b.y});
@@ -1855,7 +1870,7 @@ namespace sdhip
             return Blk8{make_float4(a0.re, a0.im, a1.re, a1.im), make_float4(a2.re, a2.im, a3.re, a3.im), make_float4(a4.re, a4.im, a5.re, a5.im),
                         make_float4(a6.re, a6.im, a7.re, a7.im)};
         }
-        __device__ static __forceinline__ cf32 step(S &s, const P &p, const cf32 v) { return Cos::step(s.cos, p.cos, AgcFirStageT<FAST>::step(s.af, p.af, v)); }
+        __device__ static __forceinline__ cf32 step(S &s, const P &p, const cf32 v) { return Cos::step(s.cos, p.cos, AgcFirStageT<FAST, MAG>::step(s.af, p.af, v)); }
     };
     __device__ __forceinline__ float sd_wrap_2pi(double ph)
     { // into the loop's own range [-2 pi, 2 pi] (costas_loop.cpp:55-58 keeps it there)
@@ -1870,10 +1885,16 @@ namespace sdhip
     // (exact start state) stops at the first checkpoint at which its AGC has merged with the earlier run's (the AGC certificate's rule)
     // and its carrier loop is inside the Costas windows in the earlier run's frame: from there on the earlier output and end state stand.
     // Warm-up tail and chunk are ONE loop over AfcFull (stores begin at the chunk start, where the state is also left in spec[k]).
-    template <int ORDER, bool FAST>
+    // The variants of k_afc: the detector's ORDER and one flag word V, an OR of (who sets the flag: launch_afc)
+    constexpr unsigned AFC_FAST = 1,  // the chunk-parallel mode's arithmetic (launch_afc's `fast`; without it every operation is rounded where the reference's is)
+                       AFC_INMAG = 2; // the gain follows |input| (AgcParams::input_mag, the ndsp fast AGC) instead of |output|: one magnitude path per instance, no test per sample
+    template <int ORDER, unsigned V>
     __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_afc(const cf32 *x, cf32 *y, ChunkGeom g, AfcParams p, const AfcState *start0, AfcState *spec, AfcState *endst,
                                                 const int *redo, int nredo, AfcCkpt *ck, int ck_per_chunk, int ck_len, float tol_phase, float tol_freq, int coop_nb)
     {
+        constexpr bool FAST = V & AFC_FAST;
+        constexpr int MAG = (V & AFC_INMAG) ? AGC_MAG_IN : AGC_MAG_OUT;
+        static_assert((V & ~(AFC_FAST | AFC_INMAG)) == 0, "AFC_*");
         __shared__ __attribute__((aligned(16))) char coop_lds[2 * COOP_LDS_BYTES];
         const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
         // Main launch with cooperative access (coop_nb > 0, see Coop): blocks 0 .. coop_nb-1 take the chunks 1 + 64 blk + lane -- all of them ordinary chunks, a
@@ -1927,9 +1948,9 @@ namespace sdhip
                 s.af = AgcFirStage::init(p.af, k);
                 s.cos = CostasState{0.0f, p.cos.init_freq};
                 if (coop)
-                    run_range1<AfcAgcOnly<FAST>, true>(s, p, x, y, w0, b - g.W, never, 0, 1 << 30, nohook, &co);
+                    run_range1<AfcAgcOnly<FAST, MAG>, true>(s, p, x, y, w0, b - g.W, never, 0, 1 << 30, nohook, &co);
                 else
-                    run_range1<AfcAgcOnly<FAST>>(s, p, x, y, w0, b - g.W, never, 0, 1 << 30, nohook);
+                    run_range1<AfcAgcOnly<FAST, MAG>>(s, p, x, y, w0, b - g.W, never, 0, 1 << 30, nohook);
                 i0 = b - g.W;
                 if (p.cos.est_len > 0 && ORDER <= 4)
                 {
@@ -1942,9 +1963,9 @@ namespace sdhip
                     e.ar = 0.0f;
                     e.ai = 0.0f;
                     if (coop)
-                        run_range1<AfcEst<M, FAST>, true>(e, p, x, y, i0, i0 + p.cos.est_len, never, 0, 1 << 30, nohook, &co);
+                        run_range1<AfcEst<M, FAST, MAG>, true>(e, p, x, y, i0, i0 + p.cos.est_len, never, 0, 1 << 30, nohook, &co);
                     else
-                        run_range1<AfcEst<M, FAST>>(e, p, x, y, i0, i0 + p.cos.est_len, never, 0, 1 << 30, nohook);
+                        run_range1<AfcEst<M, FAST, MAG>>(e, p, x, y, i0, i0 + p.cos.est_len, never, 0, 1 << 30, nohook);
                     s = e.s;
                     // BPSK symbols sit on the real axis (x^2 -> +1), QPSK symbols on the diagonals (x^4 -> -1); the sum's angle is M
                     // times the carrier phase at the first sample of the window, the loop takes over est_len samples later
@@ -1983,9 +2004,9 @@ namespace sdhip
             return false;
         };
         if (coop) // (never a re-run launch: the hook stops nobody)
-            run_range1<AfcFull<ORDER, FAST>, true>(s, p, x, y, i0, e, b, b, ck_len, hook, &co);
+            run_range1<AfcFull<ORDER, FAST, MAG>, true>(s, p, x, y, i0, e, b, b, ck_len, hook, &co);
         else
-            run_range1<AfcFull<ORDER, FAST>>(s, p, x, y, i0, e, b, b, ck_len, hook);
+            run_range1<AfcFull<ORDER, FAST, MAG>>(s, p, x, y, i0, e, b, b, ck_len, hook);
         if (!merged)
             endst[k] = s;
     }
@@ -1999,9 +2020,9 @@ namespace sdhip
         std::optional<ProfScope> _pr;
         if (redo)
             _pr.emplace("k_afc (re-run launches, included in k_afc)", st);
-        auto go = [&](auto order, auto fm) {
-            constexpr int O = decltype(order)::value;
-            constexpr bool F = decltype(fm)::value;
+        // the variant (see the AFC_* flags at k_afc) from the stage's parameters
+        const unsigned v = (fast ? AFC_FAST : 0) | (p.af.agc.input_mag ? AFC_INMAG : 0);
+        auto go = [&](auto kern) {
             // ck_len is also the spacing at which the lane looks for the chunk start (spec snapshot): always a power of two >= 32
             // cooperative access of the wave's 64 streams (see Coop): every stage range a whole number of 128-byte bursts (chunk length, warm-ups, estimator
             // window: multiples of 16 samples), every chunk from 1 on with its whole warm-up inside the call, and at least one full wave of ordinary chunks
@@ -2014,21 +2035,27 @@ namespace sdhip
                 throw HipError("k_afc: cooperative access asked for (SDHIP_COOP_REQUIRE) but the geometry does not allow it");
             if (getenv("SDHIP_DEBUG") && !redo)
                 fprintf(stderr, "[sdhip] k_afc: K %d L %d W %d w_agc %d est %d -> %d cooperative blocks of %d\n", g.K, g.L, g.W, p.w_agc, p.cos.est_len, coop_nb, nblk);
-            hipLaunchKernelGGL((k_afc<O, F>), dim3(nblk), dim3(64), 0, st, x, y, g, p, start0, spec, endst, redo, nredo, ck.ck, ck.per_chunk,
+            hipLaunchKernelGGL(kern, dim3(nblk), dim3(64), 0, st, x, y, g, p, start0, spec, endst, redo, nredo, ck.ck, ck.per_chunk,
                                ck.len > 0 ? ck.len : 2048, ck.tol_phase, ck.tol_freq, coop_nb);
         };
-        auto by_order = [&](auto fm) {
-            if (p.cos.order == 2)
-                go(std::integral_constant<int, 2>{}, fm);
-            else if (p.cos.order == 4)
-                go(std::integral_constant<int, 4>{}, fm);
-            else
-                go(std::integral_constant<int, 8>{}, fm);
-        };
-        if (fast)
-            by_order(std::true_type{});
-        else
-            by_order(std::false_type{});
+        // every instance of k_afc, once. The engine reaches six: the fused stage exists for the legacy chain alone (demod_engine.hip, fuse_agc_fir: the ndsp chain
+        // filters in front of its AGC, the DVB-S2 front end and the real-valued chains have no such stage), and that chain's AGC follows |output| under the cap
+        // of 65536. An instance is ~130 KB of code and a good part of the library's build time: AFC_INMAG has none until a caller needs it -- its line goes
+        // here -- and asking for it is an error, not a slower path.
+        const int order = p.cos.order == 2 ? 2 : p.cos.order == 4 ? 4 : 8;
+#define AFC_INSTANCE(O, V) case ((O) << 8 | (V)): return go(k_afc<(O), (V)>);
+        switch ((unsigned)order << 8 | v)
+        {
+            AFC_INSTANCE(2, AFC_FAST)
+            AFC_INSTANCE(4, AFC_FAST) // the timed step
+            AFC_INSTANCE(8, AFC_FAST)
+            AFC_INSTANCE(2, 0u) // exact mode
+            AFC_INSTANCE(4, 0u)
+            AFC_INSTANCE(8, 0u)
+        default:
+            throw HipError("k_afc: no instance for this combination of variant flags (the gain following |input|: no caller of the fused stage has it)");
+        }
+#undef AFC_INSTANCE
     }
 
     // B_k = sum over the chunk of beta^(len-1-i) * alpha * x_i, in double: thread t takes the samples i = t (mod 256) -- coalesced --
@@ -2199,7 +2226,8 @@ namespace sdhip
                                    0, 0, 0.0f, 0.0f, (unsigned long long *)nullptr);
         };
         if (p.fast) // chunk-parallel mode's arithmetic (hardware square root, one fma): the serial chain per sample is what a slow loop's
-            (getenv("SDHIP_AGC_DEPTH") && depth != 8) ? go(AgcStageT<4, true>{}) : go(AgcStageT<8, true>{}); // (measured: 28.7 -> 25.0 ms with 8 blocks per group) long warm-up costs (the ndsp block's rate 1e-4: 6e5 sequential steps per lane)
+            // (the default depth names its magnitude path, as k_afc does: two small instances for one)
+            (getenv("SDHIP_AGC_DEPTH") && depth != 8) ? go(AgcStageT<4, true>{}) : p.input_mag ? go(AgcStageT<8, true, AGC_MAG_IN>{}) : go(AgcStageT<8, true, AGC_MAG_OUT>{}); // (measured: 28.7 -> 25.0 ms with 8 blocks per group) long warm-up costs (the ndsp block's rate 1e-4: 6e5 sequential steps per lane)
         else if (depth == 8)
             go(AgcStageT<8>{});
         else if (depth == 2)
