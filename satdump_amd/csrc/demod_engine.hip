@@ -979,12 +979,12 @@ namespace sdhip
             if (cfg.exact || (nd.only == SDHIP_NDSP_MM_FAST && st == ST_MM)) // (the _fast clock recovery's own lanes are mmfast_stage's; here it is one sequential lane)
                 return 1 << 30;
             if (cfg.chunk_len <= 0 && getenv("SDHIP_CHUNK"))
-                return (int)((env_int("SDHIP_CHUNK", 8192) + 7) / 8 * 8);
+                return (int)round_up(env_int("SDHIP_CHUNK", 8192), 8);
             if (cfg.chunk_len > 0)
-                return (cfg.chunk_len + 7) / 8 * 8; // stage chunk boundaries stay multiples of 8 samples (64-byte blocks)
+                return (int)round_up(cfg.chunk_len, 8); // stage chunk boundaries stay multiples of 8 samples (64-byte blocks)
             static const char *lnames[3] = {"SDHIP_CHUNK_AGC", "SDHIP_CHUNK_COSTAS", "SDHIP_CHUNK_MM"};
             if (getenv(lnames[st]))
-                return (int)((env_int(lnames[st], 8192) + 7) / 8 * 8);
+                return (int)round_up(env_int(lnames[st], 8192), 8);
             static const char *names[3] = {"SDHIP_LANES_AGC", "SDHIP_LANES_COSTAS", "SDHIP_LANES_MM"};
             // M&M: one wave per SIMD. Round 3 / 4 ran 98 304 lanes (one and a half waves: 13.0 ms against 15.5 at 65 280 on MetOp); since the symbol loop's
             // wave-uniform fast paths (round 5: 185 -> 86 instructions per symbol) a lone wave per SIMD is no slower per lane than two sharing one, and the
@@ -992,8 +992,7 @@ namespace sdhip
             static const long long dflt[3] = {65280, 65280, 65280};
             static const long long min_len[3] = {2048, 2048, 2048};
             long long lanes = std::max<long long>(64, env_int(names[st], dflt[st]));
-            long long L = (n + lanes - 1) / lanes;
-            L = (L + 63) / 64 * 64;
+            const long long L = round_up((n + lanes - 1) / lanes, 64);
             return (int)std::min<long long>(std::max<long long>(L, min_len[st]), 1 << 20);
         }
 
@@ -1058,6 +1057,7 @@ namespace sdhip
                 specfix(d_fails.p, nf);
                 relaunch(d_fails.p, nf);
             }
+            stats.chunks += (unsigned)K; // every lane stage is judged here exactly once per call
             stats.chunks_fixed += reruns;
             stats.chunks_inexact += (unsigned)h_vout.p->inexact;
             stats.chunks_rotated += (unsigned)h_vout.p->rotated;
@@ -1066,6 +1066,178 @@ namespace sdhip
                 fprintf(stderr, "[sdhip] %-6s chunks %d  re-run %u in %u round(s)  accepted-by-tolerance %d  let through unlocked %d\n", stage, K, reruns, rounds,
                         h_vout.p->inexact, h_vout.p->forced);
             return *h_vout.p;
+        }
+        // ... for a stage whose re-run lanes start from the predecessor's end state as it is
+        template <class S, class Verdict, class Launch>
+        VerdictOut verify_fix(const char *stage, const int &K, S *spec, S *endst, Verdict verdict, Launch relaunch) // (both arrays as the stage holds them: S *)
+        {
+            return verify_fix(stage, K, verdict, [&](const int *list, int nr) { spec_from_prev(list, nr, spec, endst); }, relaunch);
+        }
+
+        // ---- what the lane stages below share: each rule of the schedule once ----------------------------------------------------------
+        static long long round_up(long long x, long long m) { return (x + m - 1) / m * m; }
+        static dim3 verdict_grid(int K) { return dim3((K + 255) / 256); } // one thread per boundary (or per entry of a re-run list), 256 a block
+        // a lane runs W + L samples in sequence, so with the chunk length left to the engine a chunk is at least half the warm-up: the lanes' work stays under 3 n
+        // (stage_env: the stage's own SDHIP_CHUNK_* override, which fixes the chunk like cfg.chunk_len and SDHIP_CHUNK do)
+        int chunk_for_warmup(int L, long long W, const char *stage_env) const
+        {
+            if (cfg.exact || cfg.chunk_len > 0 || getenv("SDHIP_CHUNK") || getenv(stage_env))
+                return L;
+            return (int)std::min<long long>(std::max<long long>(L, round_up(W / 2, 64)), 1 << 22);
+        }
+        template <class S>
+        void spec_from_prev(const int *list, int nr, S *spec, const S *endst)
+        {
+            hipLaunchKernelGGL(k_spec_from_prev<S>, verdict_grid(nr), dim3(256), 0, stream, list, nr, spec, endst);
+        }
+        template <class S, class... More>
+        void spec_from_prev(const int *list, int nr, S *spec, const S *endst, More... more)
+        { // a stage with several state arrays: in the order given
+            spec_from_prev(list, nr, spec, endst);
+            spec_from_prev(list, nr, more...);
+        }
+        // carried state: to the device before the first launch; chunk K - 1's end state back behind the last one (and the stream has drained)
+        template <class S>
+        void upload(S *dev, const S &host)
+        {
+            SD_HIP(hipMemcpyAsync(dev, &host, sizeof(S), hipMemcpyHostToDevice, stream));
+        }
+        template <class H, class S>
+        void fetch_last(H &host, const S *d_end, int K)
+        { // (H: the state itself, or the leading member of it that the host keeps)
+            SD_HIP(hipMemcpyAsync(&host, d_end + (K - 1), sizeof(H), hipMemcpyDeviceToHost, stream));
+            SD_HIP(hipStreamSynchronize(stream));
+        }
+        // checkpoints for the early exit of re-run lanes: one every 2048 samples of a chunk. work_slot: the stage's SDHIP_DEBUG work counters in d_ck_work (0 agc,
+        // 1 costas; the AGC stage, first of a call, clears both)
+        template <class Ck, class C>
+        void ckpt_rows(Ck &ck, DevBuf<C> &buf, int K, int L)
+        {
+            ck.len = 2048;
+            ck.per_chunk = L / ck.len + 1;
+            buf.reserve((size_t)K * ck.per_chunk);
+            ck.ck = buf.p;
+        }
+        template <class C>
+        ChunkCkpt make_ckpt(DevBuf<C> &buf, const ChunkGeom &g, int L, float tol_a, float tol_b = 0, int work_slot = -1)
+        {
+            ChunkCkpt ck;
+            if (!use_ckpt)
+                return ck;
+            ckpt_rows(ck, buf, g.K, L);
+            ck.tol_a = tol_a;
+            ck.tol_b = tol_b;
+            if (work_slot >= 0 && getenv("SDHIP_DEBUG"))
+            {
+                d_ck_work.reserve(6);
+                if (work_slot == 0)
+                    SD_HIP(hipMemsetAsync(d_ck_work.p, 0, 6 * sizeof(unsigned long long), stream));
+                ck.work = d_ck_work.p + 3 * work_slot;
+            }
+            return ck;
+        }
+        // mean |x| over the head of a call (at most 2^16 samples): 64 partial sums from the device, added up here
+        double mean_of_partials(long long m)
+        {
+            double part[64];
+            SD_HIP(hipMemcpyAsync(part, d_partial.p, sizeof(part), hipMemcpyDeviceToHost, stream));
+            SD_HIP(hipStreamSynchronize(stream));
+            double sm = 0;
+            for (double v : part)
+                sm += v;
+            return sm / (double)m;
+        }
+        double head_mean_abs(const cf32 *x, long long n)
+        {
+            const long long m = std::min<long long>(n, 1 << 16);
+            ProfScope _ps("k_mean_abs", stream);
+            hipLaunchKernelGGL(k_mean_abs, dim3(64), dim3(256), 0, stream, x, m, d_partial.p);
+            return mean_of_partials(m);
+        }
+        double head_mean_abs(const float *x, long long n)
+        {
+            const long long m = std::min<long long>(n, 1 << 16);
+            launch_fmean_abs(x, m, d_partial.p, stream);
+            return mean_of_partials(m);
+        }
+        // gain the AGC's warm-up lanes start from: the carried gain; on a stream's first call reference / mean |x| over the head of the input
+        float agc_gain_estimate(const cf32 *in, long long n)
+        {
+            if (started)
+                return agc_s.gain;
+            const double mean = head_mean_abs(in, n);
+            if (!(mean > 1e-12))
+                return agc_s.gain;
+            return (float)std::min((double)(agc_p.max_gain > 0 ? agc_p.max_gain : 65536.0f), (double)agc_p.reference / mean);
+        }
+        // Many warm-ups of a carrier loop missed at first sight (verify_fix's respec hook). (a) The start frequency was off (the M-th-power estimate is weak for
+        // order 8 and at low SNR; a call may also begin in noise with the carried loop state meaningless): every lane has meanwhile run a real loop over W + L
+        // samples, and the median of their end frequencies is a far better start value. (b) The warm-up is too short for this signal's loop dynamics: double it,
+        // while the stage lets it grow (may_grow) and up to the stage's cap w_cap (the stream keeps the longer one).
+        enum RespecPlan { RESPEC_GIVE_UP, RESPEC_FREQ, RESPEC_WARMUP };
+        static RespecPlan respec_by_median(std::vector<float> &end_freqs, float loop_bw, float &init_freq, long long W, bool may_grow, long long w_cap, long long &w_learned)
+        {
+            std::nth_element(end_freqs.begin(), end_freqs.begin() + end_freqs.size() / 2, end_freqs.end());
+            const float med = end_freqs[end_freqs.size() / 2];
+            if (std::fabs(med - init_freq) > 0.05f * loop_bw)
+            {
+                init_freq = med;
+                return RESPEC_FREQ;
+            }
+            if (!may_grow || 2 * W > w_cap)
+                return RESPEC_GIVE_UP;
+            w_learned = 2 * W;
+            return RESPEC_WARMUP;
+        }
+        static std::vector<float> end_freqs_of(const std::vector<CostasState> &es)
+        {
+            std::vector<float> fr(es.size());
+            for (size_t i = 0; i < es.size(); i++)
+                fr[i] = es[i].freq;
+            return fr;
+        }
+        // rot[k] = frame of chunk k relative to the stream's: the prefix sum of the per-boundary turns d_dm (mod rot_mod) into d_rot
+        void frames_from_turns(int K)
+        {
+            const int nt = (K + 1023) / 1024;
+            d_tile_sums.reserve(nt);
+            hipLaunchKernelGGL(k_chunk_scan_sums, dim3(nt), dim3(1024), 0, stream, K, 0, d_dm.p, nullptr, nullptr, nullptr, 0, d_tile_sums.p, nullptr);
+            hipLaunchKernelGGL(k_chunk_scan_apply, dim3(nt), dim3(1024), 0, stream, K, 0, d_dm.p, rot_mod, d_rot.p, nullptr, nullptr, nullptr, d_tile_sums.p, nullptr, nullptr,
+                               nullptr);
+        }
+        // chunk k's phase = true phase + rot[k] * unit: the loop state the last chunk ended in is carried re-expressed in the stream's frame (rot 0), so that the
+        // next call starts unrotated
+        void carry_in_stream_frame(CostasState &s, int rot_last) const
+        {
+            if (rot_last == 0)
+                return;
+            double ph = (double)s.phase - rot_last * rot_unit;
+            while (ph > 2 * design::PI)
+                ph -= 2 * design::PI;
+            while (ph < -2 * design::PI)
+                ph += 2 * design::PI;
+            s.phase = (float)ph;
+        }
+        // Behind a clock recovery's lanes (counts in d_counts, hand-offs in d_skip / d_extra, rows of `cap` symbols): compaction segments d_seg, offsets d_offsets
+        // and the symbol total by prefix sum on the device; the loop state chunk K - 1 ended in comes back with the total, `inc` counted from the next call's
+        // first sample (clock_recovery_mm.cpp:123-126). Returns the total.
+        template <class S>
+        long long compact_scan(int K, int cap, long long n, S &loop, const S *d_end)
+        {
+            SD_HIP(hipMemsetAsync(d_vout.p, 0, sizeof(VerdictOut), stream));
+            const int nt = (K + 1023) / 1024;
+            d_tile_sums.reserve(nt);
+            hipLaunchKernelGGL(k_chunk_scan_sums, dim3(nt), dim3(1024), 0, stream, K, 1, nullptr, d_counts.p, d_skip.p, d_extra.p, cap, d_tile_sums.p, d_vout.p);
+            hipLaunchKernelGGL(k_chunk_scan_apply, dim3(nt), dim3(1024), 0, stream, K, 1, nullptr, 1, nullptr, d_counts.p, d_skip.p, d_extra.p, d_tile_sums.p, d_seg.p, d_offsets.p,
+                               d_vout.p);
+            SD_HIP(hipMemcpyAsync(h_vout.p, d_vout.p, sizeof(VerdictOut), hipMemcpyDeviceToHost, stream));
+            fetch_last(loop, d_end, K);
+            loop.inc -= n;
+            if (loop.inc < 0)
+                loop.inc = 0;
+            if (h_vout.p->overflow)
+                throw HipError("symbol scratch overflow");
+            return h_vout.p->total;
         }
 
         // has_carrier front-end: the carrier-tracking PLL as a speculative chunk stage (one stable point per turn: no frame to
@@ -1092,7 +1264,7 @@ namespace sdhip
             const long long w_cap = 1 << 20;
             long long W = cfg.warmup > 0 ? cfg.warmup : (long long)std::max(512.0, 24.0 / (1.414 * std::max(1e-5f, cfg.carrier_pll_bw)));
             W = std::max(W, w_cpll_learned);
-            W = (std::min<long long>(W, w_cap) + 255) / 256 * 256;
+            W = round_up(std::min<long long>(W, w_cap), 256);
             const int L = pick_L(n, ST_COSTAS);
             const double tol_phase = env_int("SDHIP_COSTAS_TOL_URAD", 10000) * 1e-6, tol_freq = env_int("SDHIP_COSTAS_TOL_NFREQ", 40000) * 1e-9;
             ChunkGeom g;
@@ -1102,57 +1274,35 @@ namespace sdhip
                 d_cpll_spec.reserve(g.K);
                 d_cpll_end.reserve(g.K);
                 d_dm.reserve(g.K);
-                if (use_ckpt)
-                {
-                    ck.len = 2048;
-                    ck.per_chunk = L / ck.len + 1;
-                    d_cpll_ck.reserve((size_t)g.K * ck.per_chunk);
-                    ck.ck = d_cpll_ck.p;
-                    ck.tol_a = (float)tol_phase;
-                    ck.tol_b = (float)tol_freq;
-                }
+                ck = make_ckpt(d_cpll_ck, g, L, (float)tol_phase, (float)tol_freq);
             };
+            auto launch = [&](const int *redo, int nr) { launch_pll(in, out, g, cpll_p, d_cpll_start.p, d_cpll_spec.p, d_cpll_end.p, redo, nr, stream, ck); };
             setup(W);
-            SD_HIP(hipMemcpyAsync(d_cpll_start.p, &cpll_s, sizeof(cpll_s), hipMemcpyHostToDevice, stream));
-            launch_pll(in, out, g, cpll_p, d_cpll_start.p, d_cpll_spec.p, d_cpll_end.p, nullptr, 0, stream, ck);
+            upload(d_cpll_start.p, cpll_s);
+            launch(nullptr, 0);
             verify_fix(
                 "cpll", g.K,
                 [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_costas_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_cpll_spec.p, d_cpll_end.p, 2.0 * design::PI, 1, tol_phase,
-                                       tol_phase, tol_freq, d_dm.p, vo, fails, force);
+                    hipLaunchKernelGGL(k_costas_verdict, verdict_grid(g.K), dim3(256), 0, stream, g.K, d_cpll_spec.p, d_cpll_end.p, 2.0 * design::PI, 1, tol_phase, tol_phase,
+                                       tol_freq, d_dm.p, vo, fails, force);
                 },
-                [&](const int *list, int nr) {
-                    // a re-run starts from the predecessor's end state as it is: with one stable point per turn the earlier run's
-                    // checkpoints are in the same frame (the early-exit test compares modulo 2 pi)
-                    hipLaunchKernelGGL(k_spec_from_prev<CostasState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_cpll_spec.p, d_cpll_end.p);
-                },
-                [&](const int *redo, int nr) { launch_pll(in, out, g, cpll_p, d_cpll_start.p, d_cpll_spec.p, d_cpll_end.p, redo, nr, stream, ck); },
+                // a re-run starts from the predecessor's end state as it is: with one stable point per turn the earlier run's
+                // checkpoints are in the same frame (the early-exit test compares modulo 2 pi)
+                [&](const int *list, int nr) { spec_from_prev(list, nr, d_cpll_spec.p, d_cpll_end.p); }, launch,
                 [&](int) {
-                    // many warm-ups missed: the start frequency was off (take the median of the lanes' end frequencies) or the
-                    // warm-up is too short for this loop bandwidth (double it; the stream keeps the longer one)
                     std::vector<CostasState> es((size_t)g.K);
                     SD_HIP(hipMemcpyAsync(es.data(), d_cpll_end.p, es.size() * sizeof(CostasState), hipMemcpyDeviceToHost, stream));
                     SD_HIP(hipStreamSynchronize(stream));
-                    std::vector<float> fr(es.size());
-                    for (size_t i = 0; i < es.size(); i++)
-                        fr[i] = es[i].freq;
-                    std::nth_element(fr.begin(), fr.begin() + fr.size() / 2, fr.end());
-                    const float med = fr[fr.size() / 2];
-                    if (std::fabs(med - cpll_p.init_freq) > 0.05f * cfg.carrier_pll_bw)
-                        cpll_p.init_freq = med;
-                    else if (cfg.warmup <= 0 && 2 * (long long)g.W <= w_cap)
-                    {
-                        w_cpll_learned = 2 * (long long)g.W;
-                        setup(w_cpll_learned);
-                    }
-                    else
+                    std::vector<float> fr = end_freqs_of(es);
+                    const RespecPlan plan = respec_by_median(fr, cfg.carrier_pll_bw, cpll_p.init_freq, g.W, cfg.warmup <= 0, w_cap, w_cpll_learned);
+                    if (plan == RESPEC_GIVE_UP)
                         return false;
-                    launch_pll(in, out, g, cpll_p, d_cpll_start.p, d_cpll_spec.p, d_cpll_end.p, nullptr, 0, stream, ck);
+                    if (plan == RESPEC_WARMUP)
+                        setup(w_cpll_learned);
+                    launch(nullptr, 0);
                     return true;
                 });
-            stats.chunks += g.K;
-            SD_HIP(hipMemcpyAsync(&cpll_s, d_cpll_end.p + (g.K - 1), sizeof(cpll_s), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream));
+            fetch_last(cpll_s, d_cpll_end.p, g.K);
         }
 
         // Chunk-parallel DC block (see demod_kernels.h): affine scan in double for the accumulator at every chunk start, then the
@@ -1167,37 +1317,54 @@ namespace sdhip
             d_dc_end.reserve(g.K);
             d_dc_starts.reserve(g.K);
             launch_dc_partial(in, g, d_dc_partial.p, stream);
-            std::vector<double> part(2 * (size_t)g.K);
-            SD_HIP(hipMemcpyAsync(part.data(), d_dc_partial.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream));
-            std::vector<DcState> starts((size_t)g.K);
-            const double beta = (double)(1.0f - 0.0001f);
-            double sr = carried.acc_re, si = carried.acc_im;
-            for (int k = 0; k < g.K; k++)
-            {
-                starts[k] = DcState{(float)sr, (float)si};
-                const double a = std::pow(beta, (double)(chunk_end(g, k) - chunk_begin(g, k)));
-                sr = a * sr + part[2 * (size_t)k];
-                si = a * si + part[2 * (size_t)k + 1];
-            }
-            starts[0] = carried; // chunk 0 starts from the carried state itself
-            SD_HIP(hipMemcpyAsync(d_dc_starts.p, starts.data(), starts.size() * sizeof(DcState), hipMemcpyHostToDevice, stream));
-            SD_HIP(hipMemcpyAsync(d_dc.p, &carried, sizeof(carried), hipMemcpyHostToDevice, stream));
+            std::vector<DcState> starts;
+            dc_scan_starts(g, carried, 2, starts);
+            upload(d_dc.p, carried);
             const DcParams dp{d_dc_starts.p};
-            launch_dcblock(in, out, g, dp, d_dc.p, d_dc_spec.p, d_dc_end.p, nullptr, 0, stream);
+            auto launch = [&](const int *redo, int nr) { launch_dcblock(in, out, g, dp, d_dc.p, d_dc_spec.p, d_dc_end.p, redo, nr, stream); };
+            launch(nullptr, 0);
             const float dc_tol = 1e-5f;
             verify_fix(
-                "dc", g.K,
+                "dc", g.K, d_dc_spec.p, d_dc_end.p,
                 [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_dc_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_dc_spec.p, d_dc_end.p, dc_tol, vo, fails, force);
+                    hipLaunchKernelGGL(k_dc_verdict, verdict_grid(g.K), dim3(256), 0, stream, g.K, d_dc_spec.p, d_dc_end.p, dc_tol, vo, fails, force);
                 },
-                [&](const int *list, int nr) {
-                    hipLaunchKernelGGL(k_spec_from_prev<DcState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_dc_spec.p, d_dc_end.p);
-                },
-                [&](const int *redo, int nr) { launch_dcblock(in, out, g, dp, d_dc.p, d_dc_spec.p, d_dc_end.p, redo, nr, stream); });
-            stats.chunks += g.K;
-            SD_HIP(hipMemcpyAsync(&carried, d_dc_end.p + (g.K - 1), sizeof(carried), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream));
+                launch);
+            fetch_last(carried, d_dc_end.p, g.K);
+        }
+        // the DC block of either mode, in -> out, `carried` = the accumulator across calls
+        void dc_block(const cf32 *in, cf32 *out, long long n, DcState &carried)
+        {
+            if (!cfg.exact)
+                return dc_block_chunked(in, out, n, carried);
+            upload(d_dc.p, carried);
+            launch_dcblock_seq(in, out, n, d_dc.p, stream);
+            fetch_last(carried, d_dc.p, 1);
+        }
+        // Accumulator at every chunk start by the affine scan (demod_kernels.h), for the complex block (ncomp 2) and CorrectIQBlock<float> (ncomp 1: acc_re alone):
+        // the per-chunk sums in d_dc_partial, ncomp doubles per chunk, chained here in double over the K chunks from the carried state, which chunk 0 starts from
+        // itself; into d_dc_starts. (`starts` is the caller's: it outlives the copy.)
+        void dc_scan_starts(const ChunkGeom &g, const DcState &carried, int ncomp, std::vector<DcState> &starts)
+        {
+            starts.resize((size_t)g.K);
+            if (ncomp == 2 || g.K > 1) // (the float stage passes over a one-chunk call's sums)
+            {
+                std::vector<double> part((size_t)ncomp * (size_t)g.K);
+                SD_HIP(hipMemcpyAsync(part.data(), d_dc_partial.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+                SD_HIP(hipStreamSynchronize(stream));
+                const double beta = (double)(1.0f - 0.0001f);
+                double sr = carried.acc_re, si = ncomp == 2 ? carried.acc_im : 0.0;
+                for (int k = 0; k < g.K; k++)
+                {
+                    starts[k] = DcState{(float)sr, (float)si};
+                    const double a = std::pow(beta, (double)(chunk_end(g, k) - chunk_begin(g, k)));
+                    sr = a * sr + part[(size_t)ncomp * (size_t)k];
+                    if (ncomp == 2)
+                        si = a * si + part[2 * (size_t)k + 1];
+                }
+            }
+            starts[0] = carried;
+            SD_HIP(hipMemcpyAsync(d_dc_starts.p, starts.data(), starts.size() * sizeof(DcState), hipMemcpyHostToDevice, stream));
         }
 
         // AGC + RRC filter + Costas loop as ONE speculative lane stage (k_afc), in -> out (the Costas output in per-chunk frames; cg =
@@ -1208,27 +1375,11 @@ namespace sdhip
         void afc_chunked(const cf32 *in, cf32 *out, long long n, ChunkGeom &cg)
         {
             // ---- AGC part of the warm-up (see the stand-alone AGC stage below for the reasoning)
-            float g_est = agc_s.gain;
-            if (!started)
-            {
-                const long long m = std::min<long long>(n, 1 << 16);
-                ProfScope _ps("k_mean_abs", stream);
-                hipLaunchKernelGGL(k_mean_abs, dim3(64), dim3(256), 0, stream, in, m, d_partial.p);
-                double part[64];
-                SD_HIP(hipMemcpyAsync(part, d_partial.p, sizeof(part), hipMemcpyDeviceToHost, stream));
-                SD_HIP(hipStreamSynchronize(stream));
-                double sm = 0;
-                for (double v : part)
-                    sm += v;
-                const double mean = sm / (double)m;
-                if (mean > 1e-12)
-                    g_est = (float)std::min((double)(agc_p.max_gain > 0 ? agc_p.max_gain : 65536.0f), (double)agc_p.reference / mean);
-            }
+            const float g_est = agc_gain_estimate(in, n);
             const double tau = std::max(1.0f, g_est) / std::max(1e-6f, cfg.agc_rate);
             long long Wa = cfg.warmup > 0 ? cfg.warmup : (long long)(24.0 * tau);
             Wa = env_int("SDHIP_W_AGC", Wa);
-            Wa = std::min<long long>(std::max<long long>(Wa, 1024), 1 << 22);
-            Wa = (Wa + 255) / 256 * 256;
+            Wa = round_up(std::min<long long>(std::max<long long>(Wa, 1024), 1 << 22), 256);
             agc_p.init_gain = g_est;
             af_p.agc = agc_p;
             // ---- start frequency of the carrier loop's warm-ups: this stream's tracked frequency; on the very first call the M-th power
@@ -1287,10 +1438,10 @@ namespace sdhip
             // and nothing at 20 (0.00393 against 0.00389 beyond 1e-5).
             const double taus = (double)env_int("SDHIP_COSTAS_TAUS", 20);
             long long W = cfg.warmup > 0 ? cfg.warmup : (long long)std::max(512.0, taus / (1.414 * std::max(1e-5f, cfg.pll_bw)));
-            const long long w_first = (W + 255) / 256 * 256;
+            const long long w_first = round_up(W, 256);
             W = std::max(W, w_cos_learned);
             W = env_int("SDHIP_W_COSTAS", W);
-            W = (std::min<long long>(W, w_cos_cap) + 255) / 256 * 256;
+            W = round_up(std::min<long long>(W, w_cos_cap), 256);
             // two waves per SIMD: the stage is bound by its dependent chains (AGC sqrt, sincos in double), not by its loads -- measured
             // (MetOp, profiles/history/r03/r03_a_ab_metop.txt): 26.4 ms with 65 280 lanes, 21.3 with 98 304, 19.5 with 130 560 (226 VGPRs: two waves fit)
             // Round 6: one wave per SIMD instead where that is the faster plan. A lane's time is (warm-up + chunk) sequential samples at the per-sample pace of
@@ -1309,8 +1460,8 @@ namespace sdhip
             const long long lanes = std::max<long long>(64, env_int("SDHIP_LANES_AFC", lanes_dflt));
             int L = pick_L(n, ST_COSTAS);
             if (!cfg.exact && cfg.chunk_len <= 0 && !getenv("SDHIP_CHUNK") && !getenv("SDHIP_CHUNK_COSTAS") && !getenv("SDHIP_LANES_COSTAS"))
-                L = (int)std::min<long long>(std::max<long long>(((n + lanes - 1) / lanes + 63) / 64 * 64, 2048), 1 << 20);
-            L = (int)(((long long)L + 63) / 64 * 64); // chunk starts on whole load groups (the lane finds its chunk start on a group boundary)
+                L = (int)std::min<long long>(std::max<long long>(round_up((n + lanes - 1) / lanes, 64), 2048), 1 << 20);
+            L = (int)round_up(L, 64); // chunk starts on whole load groups (the lane finds its chunk start on a group boundary)
             const double tol_phase = env_int("SDHIP_COSTAS_TOL_URAD", 10000) * 1e-6, tol_freq = env_int("SDHIP_COSTAS_TOL_NFREQ", 40000) * 1e-9;
             // the hand-off window proper (round 6; see costas_stage): a boundary between it and the wide window is re-run from the exact state and stops at the first
             // checkpoint at which it is back within it
@@ -1332,77 +1483,71 @@ namespace sdhip
                 ck.tol_phase = (float)tol_tight;
                 ck.tol_freq = (float)tol_freq;
                 if (use_ckpt && !cfg.exact)
-                {
-                    ck.per_chunk = L / ck.len + 1;
-                    d_afc_ck.reserve((size_t)cg.K * ck.per_chunk);
-                    ck.ck = d_afc_ck.p;
-                }
+                    ckpt_rows(ck, d_afc_ck, cg.K, L);
                 d_rot.reserve(cg.K);
                 d_dm.reserve(cg.K);
             };
+            auto launch = [&](const int *redo, int nr) { launch_afc(in, out, cg, ap, d_afc_start.p, d_afc_spec.p, d_afc_end.p, redo, nr, stream, ck, afc_fast); };
             setup(W);
             // the carried start state lives on the device (filter window); its carrier part is the host's copy (kept in the stream's frame)
-            SD_HIP(hipMemcpyAsync(&d_afc_start.p->cos, &cos_s, sizeof(cos_s), hipMemcpyHostToDevice, stream));
-            launch_afc(in, out, cg, ap, d_afc_start.p, d_afc_spec.p, d_afc_end.p, nullptr, 0, stream, ck, afc_fast);
+            upload(&d_afc_start.p->cos, cos_s);
+            launch(nullptr, 0);
             verify_fix(
                 "afc", cg.K,
                 [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_afc_verdict, dim3((cg.K + 255) / 256), dim3(256), 0, stream, cg.K, d_afc_spec.p, d_afc_end.p, rot_unit, rot_mod, tol_phase, tol_tight, tol_freq,
+                    hipLaunchKernelGGL(k_afc_verdict, verdict_grid(cg.K), dim3(256), 0, stream, cg.K, d_afc_spec.p, d_afc_end.p, rot_unit, rot_mod, tol_phase, tol_tight, tol_freq,
                                        d_dm.p, vo, fails, force);
                 },
                 [&](const int *list, int nr) {
-                    hipLaunchKernelGGL(k_afc_spec_fix, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_afc_spec.p, d_afc_end.p, rot_unit, use_ckpt ? 1 : 0);
+                    hipLaunchKernelGGL(k_afc_spec_fix, verdict_grid(nr), dim3(256), 0, stream, list, nr, d_afc_spec.p, d_afc_end.p, rot_unit, use_ckpt ? 1 : 0);
                 },
-                [&](const int *redo, int nr) { launch_afc(in, out, cg, ap, d_afc_start.p, d_afc_spec.p, d_afc_end.p, redo, nr, stream, ck, afc_fast); },
+                launch,
                 [&](int) {
-                    // many warm-ups missed: start frequency off (take the median of the lanes' end frequencies) or warm-up too short for
-                    // this signal's loop dynamics (double it; the stream keeps the longer one) -- see the stand-alone Costas stage
                     std::vector<float> fr((size_t)cg.K);
                     d_afc_freq.reserve(cg.K);
-                    hipLaunchKernelGGL(k_afc_gather_freq, dim3((cg.K + 255) / 256), dim3(256), 0, stream, cg.K, d_afc_end.p, d_afc_freq.p);
+                    hipLaunchKernelGGL(k_afc_gather_freq, verdict_grid(cg.K), dim3(256), 0, stream, cg.K, d_afc_end.p, d_afc_freq.p);
                     SD_HIP(hipMemcpyAsync(fr.data(), d_afc_freq.p, fr.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
                     SD_HIP(hipStreamSynchronize(stream));
-                    std::nth_element(fr.begin(), fr.begin() + fr.size() / 2, fr.end());
-                    const float med = fr[fr.size() / 2];
-                    if (std::fabs(med - cos_p.init_freq) > 0.05f * cfg.pll_bw)
-                        cos_p.init_freq = med;
-                    else if (cfg.warmup <= 0 && !getenv("SDHIP_W_COSTAS") && 2 * (long long)cg.W <= std::min(w_cos_cap, 4 * w_first))
-                        w_cos_learned = 2 * (long long)cg.W; // (at most twice: a stream that still misses is not locked -- noise -- and every
-                                                             // further doubling would only multiply the work of lanes that cannot merge)
-                    else
+                    // (the warm-up at most twice: a stream that still misses is not locked -- noise -- and every further doubling would only multiply the work of
+                    // lanes that cannot merge)
+                    if (respec_by_median(fr, cfg.pll_bw, cos_p.init_freq, cg.W, cfg.warmup <= 0 && !getenv("SDHIP_W_COSTAS"), std::min(w_cos_cap, 4 * w_first),
+                                         w_cos_learned) == RESPEC_GIVE_UP)
                         return false;
                     setup(std::max<long long>(cg.W, w_cos_learned));
-                    launch_afc(in, out, cg, ap, d_afc_start.p, d_afc_spec.p, d_afc_end.p, nullptr, 0, stream, ck, afc_fast);
+                    launch(nullptr, 0);
                     return true;
                 },
                 true);
-            stats.chunks += 2 * (unsigned)cg.K; // the chunks of two loop stages
-            {
-                const int nt = (cg.K + 1023) / 1024;
-                d_tile_sums.reserve(nt);
-                hipLaunchKernelGGL(k_chunk_scan_sums, dim3(nt), dim3(1024), 0, stream, cg.K, 0, d_dm.p, nullptr, nullptr, nullptr, 0, d_tile_sums.p, nullptr);
-                hipLaunchKernelGGL(k_chunk_scan_apply, dim3(nt), dim3(1024), 0, stream, cg.K, 0, d_dm.p, rot_mod, d_rot.p, nullptr, nullptr, nullptr, d_tile_sums.p,
-                                   nullptr, nullptr, nullptr);
-            }
+            stats.chunks += (unsigned)cg.K; // the chunks of two loop stages: verify_fix has counted them once
+            frames_from_turns(cg.K);
             int rot_last = 0;
             SD_HIP(hipMemcpyAsync(d_afc_start.p, d_afc_end.p + (cg.K - 1), sizeof(AfcState), hipMemcpyDeviceToDevice, stream));
             SD_HIP(hipMemcpyAsync(&agc_s, &d_afc_end.p[cg.K - 1].af.gain, sizeof(agc_s), hipMemcpyDeviceToHost, stream));
             SD_HIP(hipMemcpyAsync(&cos_s, &d_afc_end.p[cg.K - 1].cos, sizeof(cos_s), hipMemcpyDeviceToHost, stream));
             SD_HIP(hipMemcpyAsync(&rot_last, d_rot.p + (cg.K - 1), sizeof(int), hipMemcpyDeviceToHost, stream));
             SD_HIP(hipStreamSynchronize(stream));
-            // carry the loop state re-expressed in the stream's frame (rot 0), so that the next call starts unrotated
-            if (rot_last != 0)
-            {
-                double ph = (double)cos_s.phase - rot_last * rot_unit;
-                while (ph > 2 * design::PI)
-                    ph -= 2 * design::PI;
-                while (ph < -2 * design::PI)
-                    ph += 2 * design::PI;
-                cos_s.phase = (float)ph;
-            }
+            carry_in_stream_frame(cos_s, rot_last);
             stats.freq_hz = (float)(((double)cos_s.freq / (2.0 * design::PI)) * (double)final_samplerate);
         }
 
+        // ---- the AGC's lanes (k_chunks<AgcStage>) under either schedule -- start gains scanned (ap.starts) or warmed up --: AIN -> OUT, a boundary stands with its
+        // gains within `tol` (relative); work_slot: make_ckpt's
+        void agc_lanes(const cf32 *AIN, cf32 *OUT, const ChunkGeom &g, int L, const AgcParams &ap, const char *stage, float tol, int work_slot)
+        {
+            upload(d_agc_start.p, agc_s);
+            const ChunkCkpt ck = make_ckpt(d_agc_ck, g, L, tol, 0, work_slot);
+            auto launch = [&](const int *redo, int nr) { launch_agc(AIN, OUT, g, ap, d_agc_start.p, d_agc_spec.p, d_agc_end.p, redo, nr, stream, ck); };
+            launch(nullptr, 0);
+            verify_fix(
+                stage, g.K, d_agc_spec.p, d_agc_end.p,
+                [&](VerdictOut *vo, int *fails, int force) {
+                    hipLaunchKernelGGL(k_agc_verdict, verdict_grid(g.K), dim3(256), 0, stream, g.K, d_agc_spec.p, d_agc_end.p, tol, vo, fails, force);
+                },
+                launch);
+            if (ck.work)
+                ck_report("agc", 0);
+            fetch_last(agc_s, d_agc_end.p, g.K);
+        }
         // ---- AGC with scanned start gains (see agc_stage): AIN -> OUT
         DevBuf<double> d_agc_partial;
         DevBuf<float> d_agc_starts;
@@ -1434,34 +1579,10 @@ namespace sdhip
                 return false;
             }
             SD_HIP(hipMemcpyAsync(d_agc_starts.p, starts.data(), starts.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-            SD_HIP(hipMemcpyAsync(d_agc_start.p, &agc_s, sizeof(agc_s), hipMemcpyHostToDevice, stream));
             AgcParams ap = agc_p;
             ap.starts = d_agc_starts.p;
-            ChunkCkpt agc_ck;
             const double steps = std::min((double)L, std::max(1.0, tau));
-            const float tol = (float)std::min(1e-4, std::max(1e-6, 6.0 * 3e-8 * std::sqrt(steps)));
-            if (use_ckpt)
-            {
-                agc_ck.len = 2048;
-                agc_ck.per_chunk = L / agc_ck.len + 1;
-                d_agc_ck.reserve((size_t)g.K * agc_ck.per_chunk);
-                agc_ck.ck = d_agc_ck.p;
-                agc_ck.tol_a = tol;
-            }
-            launch_agc(AIN, OUT, g, ap, d_agc_start.p, d_agc_spec.p, d_agc_end.p, nullptr, 0, stream, agc_ck);
-            const int vb = (g.K + 255) / 256;
-            verify_fix(
-                "agc-scan", g.K,
-                [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_agc_verdict, dim3(vb), dim3(256), 0, stream, g.K, d_agc_spec.p, d_agc_end.p, tol, vo, fails, force);
-                },
-                [&](const int *list, int nr) {
-                    hipLaunchKernelGGL(k_spec_from_prev<AgcState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_agc_spec.p, d_agc_end.p);
-                },
-                [&](const int *redo, int nr) { launch_agc(AIN, OUT, g, ap, d_agc_start.p, d_agc_spec.p, d_agc_end.p, redo, nr, stream, agc_ck); });
-            stats.chunks += g.K;
-            SD_HIP(hipMemcpyAsync(&agc_s, d_agc_end.p + (g.K - 1), sizeof(agc_s), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream));
+            agc_lanes(AIN, OUT, g, L, ap, "agc-scan", (float)std::min(1e-4, std::max(1e-6, 6.0 * 3e-8 * std::sqrt(steps))), -1);
             return true;
         }
 
@@ -1470,22 +1591,7 @@ namespace sdhip
         void agc_stage(const cf32 *AIN, cf32 *OUT, long long n)
         {
             // warm-up length ~ 24 time constants of the loop (tau = gain / rate samples), gain estimated from mean |x|
-            float g_est = agc_s.gain;
-            if (!started)
-            {
-                const long long m = std::min<long long>(n, 1 << 16);
-                ProfScope _ps("k_mean_abs", stream);
-                hipLaunchKernelGGL(k_mean_abs, dim3(64), dim3(256), 0, stream, AIN, m, d_partial.p);
-                double part[64];
-                SD_HIP(hipMemcpyAsync(part, d_partial.p, sizeof(part), hipMemcpyDeviceToHost, stream));
-                SD_HIP(hipStreamSynchronize(stream));
-                double s = 0;
-                for (double v : part)
-                    s += v;
-                const double mean = s / (double)m;
-                if (mean > 1e-12)
-                    g_est = (float)std::min((double)(agc_p.max_gain > 0 ? agc_p.max_gain : 65536.0f), (double)agc_p.reference / mean);
-            }
+            const float g_est = agc_gain_estimate(AIN, n);
             // tau = gain / rate samples; 24 tau of warm-up from the mean-based gain merge bit for bit with the previous chunk's
             // trajectory (13 tau would do within the 1e-6 tolerance; measured: the lane kernels are bound by their strided
             // HBM traffic, not by the chain -- a parallel-scan start value that cut W to 6 tau bought nothing net)
@@ -1495,8 +1601,7 @@ namespace sdhip
             const double taus = (double)env_int("SDHIP_AGC_TAUS", nd.on ? 14 : 24);
             long long W = cfg.warmup > 0 ? cfg.warmup : (long long)(taus * tau);
             W = env_int("SDHIP_W_AGC", W);
-            W = std::min<long long>(std::max<long long>(W, 1024), 1 << 22);
-            W = (W + 255) / 256 * 256;
+            W = round_up(std::min<long long>(std::max<long long>(W, 1024), 1 << 22), 256);
             agc_p.init_gain = g_est;
             agc_p.fast = (nd.on && !cfg.exact && env_int("SDHIP_FAST_MATH", 1) != 0) ? 1 : 0;
             int L = pick_L(n, ST_AGC);
@@ -1516,10 +1621,8 @@ namespace sdhip
             // a slow loop (the ndsp block's default rate 1e-4: 24 tau ~ 4e5 samples) on many short chunks would run K lanes over W + L
             // samples each -- a hundred times the stream through L2 / HBM for no gain in wall time, which is (W + L) sequential steps
             // either way: keep the chunk at least half the warm-up (work <= 3 n, still thousands of lanes on a bench-sized call)
-            if (!cfg.exact && cfg.chunk_len <= 0 && !getenv("SDHIP_CHUNK") && !getenv("SDHIP_CHUNK_AGC"))
-                L = (int)std::min<long long>(std::max<long long>(L, (W / 2 + 63) / 64 * 64), 1 << 22);
+            L = chunk_for_warmup(L, W, "SDHIP_CHUNK_AGC");
             const ChunkGeom g = make_geom(n, L, (int)W);
-            stats.chunks += g.K;
             if (fuse_agc_fir)
             {
                 // AGC + RRC filter in one pass: in -> OUT holds the FILTERED samples; the lane state (gain, last 30 AGC outputs)
@@ -1527,56 +1630,22 @@ namespace sdhip
                 af_p.agc = agc_p;
                 d_af_spec.reserve(g.K);
                 d_af_end.reserve(g.K);
-                launch_agc_fir(AIN, OUT, g, af_p, d_af_start.p, d_af_spec.p, d_af_end.p, nullptr, 0, stream);
-                const int vb = (g.K + 255) / 256;
+                auto launch = [&](const int *redo, int nr) { launch_agc_fir(AIN, OUT, g, af_p, d_af_start.p, d_af_spec.p, d_af_end.p, redo, nr, stream); };
+                launch(nullptr, 0);
                 verify_fix(
-                    "agc+fir", g.K,
+                    "agc+fir", g.K, d_af_spec.p, d_af_end.p,
                     [&](VerdictOut *vo, int *fails, int force) {
-                        hipLaunchKernelGGL(k_agcfir_verdict, dim3(vb), dim3(256), 0, stream, g.K, d_af_spec.p, d_af_end.p, vo, fails, force);
+                        hipLaunchKernelGGL(k_agcfir_verdict, verdict_grid(g.K), dim3(256), 0, stream, g.K, d_af_spec.p, d_af_end.p, vo, fails, force);
                     },
-                    [&](const int *list, int nr) {
-                        hipLaunchKernelGGL(k_spec_from_prev<AgcFirState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_af_spec.p, d_af_end.p);
-                    },
-                    [&](const int *redo, int nr) { launch_agc_fir(AIN, OUT, g, af_p, d_af_start.p, d_af_spec.p, d_af_end.p, redo, nr, stream); });
+                    launch);
                 SD_HIP(hipMemcpyAsync(d_af_start.p, d_af_end.p + (g.K - 1), sizeof(AgcFirState), hipMemcpyDeviceToDevice, stream));
-                SD_HIP(hipMemcpyAsync(&agc_s, d_af_end.p + (g.K - 1), sizeof(agc_s), hipMemcpyDeviceToHost, stream)); // the gain is the state's first member
-                SD_HIP(hipStreamSynchronize(stream));
+                fetch_last(agc_s, d_af_end.p, g.K); // the gain is the state's first member
             }
             else
             {
-            d_agc_spec.reserve(g.K);
-            d_agc_end.reserve(g.K);
-            SD_HIP(hipMemcpyAsync(d_agc_start.p, &agc_s, sizeof(agc_s), hipMemcpyHostToDevice, stream));
-            ChunkCkpt agc_ck;
-            if (use_ckpt)
-            {
-                agc_ck.len = 2048;
-                agc_ck.per_chunk = L / agc_ck.len + 1;
-                d_agc_ck.reserve((size_t)g.K * agc_ck.per_chunk);
-                agc_ck.ck = d_agc_ck.p;
-                agc_ck.tol_a = 1e-6f;
-                if (getenv("SDHIP_DEBUG"))
-                {
-                    d_ck_work.reserve(6);
-                    SD_HIP(hipMemsetAsync(d_ck_work.p, 0, 6 * sizeof(unsigned long long), stream));
-                    agc_ck.work = d_ck_work.p;
-                }
-            }
-            launch_agc(AIN, OUT, g, agc_p, d_agc_start.p, d_agc_spec.p, d_agc_end.p, nullptr, 0, stream, agc_ck);
-            const int vb = (g.K + 255) / 256;
-            verify_fix(
-                "agc", g.K,
-                [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_agc_verdict, dim3(vb), dim3(256), 0, stream, g.K, d_agc_spec.p, d_agc_end.p, 1e-6f, vo, fails, force);
-                },
-                [&](const int *list, int nr) {
-                    hipLaunchKernelGGL(k_spec_from_prev<AgcState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_agc_spec.p, d_agc_end.p);
-                },
-                [&](const int *redo, int nr) { launch_agc(AIN, OUT, g, agc_p, d_agc_start.p, d_agc_spec.p, d_agc_end.p, redo, nr, stream, agc_ck); });
-            if (agc_ck.work)
-                ck_report("agc", 0);
-            SD_HIP(hipMemcpyAsync(&agc_s, d_agc_end.p + (g.K - 1), sizeof(agc_s), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream));
+                d_agc_spec.reserve(g.K);
+                d_agc_end.reserve(g.K);
+                agc_lanes(AIN, OUT, g, L, agc_p, "agc", 1e-6f, 0);
             }
         }
 
@@ -1632,10 +1701,10 @@ namespace sdhip
             // merging bit for bit takes the RATE state down to its last bit: measured on the reference block, 12 - 25 k symbols at the default gains (8.7e-3), 4 - 11 k at
             // 0.02 -- 110 - 220 / gain_mu: 300 / gain_mu symbols of warm-up
             long long W = cfg.warmup > 0 ? cfg.warmup : (long long)(300.0 / gmu * final_sps);
-            W = (env_int("SDHIP_W_MMFAST", W) + 255) / 256 * 256;
+            W = round_up(env_int("SDHIP_W_MMFAST", W), 256);
             const long long lanes = std::max<long long>(64, env_int("SDHIP_LANES_MMFAST", 13056));
             long long L = cfg.chunk_len > 0 ? cfg.chunk_len : std::max<long long>(4096, (n + lanes - 1) / lanes);
-            L = (L + 63) / 64 * 64;
+            L = round_up(L, 64);
             if (L > (1 << 30) || W > (1 << 30))
                 return -1;
             const ChunkGeom g = make_geom(n, (int)L, (int)W);
@@ -1827,7 +1896,7 @@ namespace sdhip
             const int L = pick_L(n, ST_COSTAS);
             long long W = cfg.warmup > 0 ? cfg.warmup : (long long)std::max(512.0, 24.0 / (1.414 * std::max(1e-5f, cfg.pll_bw)));
             W = std::max(W, w_cos_learned); // (a stream that needed a longer warm-up keeps it)
-            W = (std::min<long long>(env_int("SDHIP_W_COSTAS", W), 1 << 20) + 255) / 256 * 256;
+            W = round_up(std::min<long long>(env_int("SDHIP_W_COSTAS", W), 1 << 20), 256);
             ChunkGeom g = make_geom(n, L, (int)W);
             if (cfg.exact || g.K < 2)
             {
@@ -2057,7 +2126,7 @@ namespace sdhip
             long long W = cfg.warmup > 0 ? cfg.warmup : (long long)std::max(512.0, 24.0 / (1.414 * std::max(1e-5f, cfg.pll_bw)));
             W = std::max(W, w_cos_learned);
             W = env_int("SDHIP_W_COSTAS", W);
-            W = (std::min<long long>(W, w_cos_cap) + 255) / 256 * 256;
+            W = round_up(std::min<long long>(W, w_cos_cap), 256);
             const int L = pick_L(n, ST_COSTAS);
             // Acceptance window of a Costas boundary = the soft-symbol parity target (1e-5 relative): a phase offset of d rad
             // is a relative symbol error of d. Two trajectories of this loop on the same samples contract onto each other down to
@@ -2086,91 +2155,49 @@ namespace sdhip
                 cg = make_geom(n, L, (int)Wn);
                 d_cos_spec.reserve(cg.K);
                 d_cos_end.reserve(cg.K);
-                if (use_ckpt)
-                {
-                    cos_ck.len = 2048;
-                    cos_ck.per_chunk = L / cos_ck.len + 1;
-                    d_cos_ck.reserve((size_t)cg.K * cos_ck.per_chunk);
-                    cos_ck.ck = d_cos_ck.p;
-                    cos_ck.tol_a = (float)tol_tight;
-                    cos_ck.tol_b = (float)tol_freq;
-                    if (getenv("SDHIP_DEBUG"))
-                    {
-                        d_ck_work.reserve(6);
-                        cos_ck.work = d_ck_work.p + 3;
-                    }
-                }
+                cos_ck = make_ckpt(d_cos_ck, cg, L, (float)tol_tight, (float)tol_freq, 1);
                 d_rot.reserve(cg.K);
                 d_dm.reserve(cg.K);
             };
+            auto launch = [&](const int *redo, int nr) { launch_costas(A, B, cg, cos_p, d_cos_start.p, d_cos_spec.p, d_cos_end.p, redo, nr, stream, cos_ck); };
             costas_setup(W);
-            SD_HIP(hipMemcpyAsync(d_cos_start.p, &cos_s, sizeof(cos_s), hipMemcpyHostToDevice, stream));
-            launch_costas(A, B, cg, cos_p, d_cos_start.p, d_cos_spec.p, d_cos_end.p, nullptr, 0, stream, cos_ck);
+            upload(d_cos_start.p, cos_s);
+            launch(nullptr, 0);
             verify_fix(
                 "costas", cg.K,
                 [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_costas_verdict, dim3((cg.K + 255) / 256), dim3(256), 0, stream, cg.K, d_cos_spec.p, d_cos_end.p, rot_unit, rot_mod, tol_phase, tol_tight, tol_freq,
+                    hipLaunchKernelGGL(k_costas_verdict, verdict_grid(cg.K), dim3(256), 0, stream, cg.K, d_cos_spec.p, d_cos_end.p, rot_unit, rot_mod, tol_phase, tol_tight, tol_freq,
                                        d_dm.p, vo, fails, force);
                 },
                 [&](const int *list, int nr) {
                     if (use_ckpt)
-                        hipLaunchKernelGGL(k_costas_spec_aligned, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_cos_spec.p, d_cos_end.p, rot_unit);
+                        hipLaunchKernelGGL(k_costas_spec_aligned, verdict_grid(nr), dim3(256), 0, stream, list, nr, d_cos_spec.p, d_cos_end.p, rot_unit);
                     else
-                        hipLaunchKernelGGL(k_spec_from_prev<CostasState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_cos_spec.p, d_cos_end.p);
+                        spec_from_prev(list, nr, d_cos_spec.p, d_cos_end.p);
                 },
-                [&](const int *redo, int nr) { launch_costas(A, B, cg, cos_p, d_cos_start.p, d_cos_spec.p, d_cos_end.p, redo, nr, stream, cos_ck); },
+                launch,
                 [&](int) {
-                    // Many warm-ups missed. (a) The start frequency was off (the M-th-power estimate is weak for order 8 and at low
-                    // SNR; a call may also begin in noise with the carried loop state meaningless): every lane has meanwhile run a
-                    // real loop over W + L samples, and the median of their end frequencies is a far better start value. (b) The
-                    // warm-up is too short for this signal's loop dynamics: double it (the stream keeps the longer one).
                     std::vector<CostasState> es((size_t)cg.K);
                     SD_HIP(hipMemcpyAsync(es.data(), d_cos_end.p, es.size() * sizeof(CostasState), hipMemcpyDeviceToHost, stream));
                     SD_HIP(hipStreamSynchronize(stream));
-                    std::vector<float> fr(es.size());
-                    for (size_t i = 0; i < es.size(); i++)
-                        fr[i] = es[i].freq;
-                    std::nth_element(fr.begin(), fr.begin() + fr.size() / 2, fr.end());
-                    const float med = fr[fr.size() / 2];
-                    if (std::fabs(med - cos_p.init_freq) > 0.05f * cfg.pll_bw)
-                        cos_p.init_freq = med;
-                    else if (cfg.warmup <= 0 && !getenv("SDHIP_W_COSTAS") && 2 * (long long)cg.W <= w_cos_cap)
-                    {
-                        w_cos_learned = 2 * (long long)cg.W;
-                        costas_setup(w_cos_learned);
-                    }
-                    else
+                    std::vector<float> fr = end_freqs_of(es);
+                    const RespecPlan plan = respec_by_median(fr, cfg.pll_bw, cos_p.init_freq, cg.W, cfg.warmup <= 0 && !getenv("SDHIP_W_COSTAS"), w_cos_cap, w_cos_learned);
+                    if (plan == RESPEC_GIVE_UP)
                         return false;
-                    launch_costas(A, B, cg, cos_p, d_cos_start.p, d_cos_spec.p, d_cos_end.p, nullptr, 0, stream, cos_ck);
+                    if (plan == RESPEC_WARMUP)
+                        costas_setup(w_cos_learned);
+                    launch(nullptr, 0);
                     return true;
                 },
                 true);
-            stats.chunks += cg.K;
             if (cos_ck.work)
                 ck_report("costas", 1);
-            // rot[k] = frame of chunk k relative to the stream's (prefix sum of the per-boundary turns)
-            {
-                const int nt = (cg.K + 1023) / 1024;
-                d_tile_sums.reserve(nt);
-                hipLaunchKernelGGL(k_chunk_scan_sums, dim3(nt), dim3(1024), 0, stream, cg.K, 0, d_dm.p, nullptr, nullptr, nullptr, 0, d_tile_sums.p, nullptr);
-                hipLaunchKernelGGL(k_chunk_scan_apply, dim3(nt), dim3(1024), 0, stream, cg.K, 0, d_dm.p, rot_mod, d_rot.p, nullptr, nullptr, nullptr, d_tile_sums.p,
-                                   nullptr, nullptr, nullptr);
-            }
+            frames_from_turns(cg.K);
             int rot_last = 0;
             SD_HIP(hipMemcpyAsync(&cos_s, d_cos_end.p + (cg.K - 1), sizeof(cos_s), hipMemcpyDeviceToHost, stream));
             SD_HIP(hipMemcpyAsync(&rot_last, d_rot.p + (cg.K - 1), sizeof(int), hipMemcpyDeviceToHost, stream));
             SD_HIP(hipStreamSynchronize(stream));
-            // chunk k's phase = true phase + rot[k]*unit; carry the loop state in the frame of the last chunk,
-            // re-expressed in the stream's frame (rot 0) so the next call starts unrotated
-            if (rot_last != 0)
-            {
-                double ph = (double)cos_s.phase - rot_last * rot_unit;
-                while (ph > 2 * design::PI)
-                    ph -= 2 * design::PI;
-                while (ph < -2 * design::PI)
-                    ph += 2 * design::PI;
-                cos_s.phase = (float)ph;
-            }
+            carry_in_stream_frame(cos_s, rot_last);
             stats.freq_hz = (float)(((double)cos_s.freq / (2.0 * design::PI)) * rate_hz);
         }
 
@@ -2223,8 +2250,7 @@ namespace sdhip
             const long long w_mm_cap = (long long)(slow * 64.0 / gmu * final_sps);
             long long W = cfg.warmup > 0 ? cfg.warmup : (long long)std::min(w_full, std::max(w_gear, 0.5 * L));
             W = std::max(W, w_learned);
-            W = env_int("SDHIP_W_MM", W);
-            W = (W + 255) / 256 * 256;
+            W = round_up(env_int("SDHIP_W_MM", W), 256);
             ChunkGeom g;
             // Hand-off windows of an M&M boundary, in samples of timing. Two trajectories of this loop on the same samples
             // hover 3e-5 ... 3e-4 sample apart (the feedback is piecewise constant in mu through the arm index), which makes
@@ -2283,9 +2309,11 @@ namespace sdhip
             if (getenv("SDHIP_PRINT_ADDR")) // experiment: the M&M launch time against where its buffers lie
                 fprintf(stderr, "[sdhip] mm buffers: in %p  symbols %p (%zu B, row %d B)  K %d L %d W %d\n", (const void *)A, (void *)symbuf.p, symbuf.cap * sizeof(cf32),
                         mm_p.cap * 8, g.K, g.L, g.W);
-            SD_HIP(hipMemcpyAsync(d_mm_start.p, &mm_s, sizeof(mm_s), hipMemcpyHostToDevice, stream));
-            launch_mm(A, symbuf.p, d_counts.p, g, mm_p, d_mm_start.p, d_mm_spec.p, d_mm_end.p, d_mm_spec_c.p, d_mm_end_c.p, nullptr, 0, stream, ckp, ck_per_chunk,
-                      (float)MM_TOL);
+            auto launch = [&](const int *redo, int nr) {
+                launch_mm(A, symbuf.p, d_counts.p, g, mm_p, d_mm_start.p, d_mm_spec.p, d_mm_end.p, d_mm_spec_c.p, d_mm_end_c.p, redo, nr, stream, ckp, ck_per_chunk, (float)MM_TOL);
+            };
+            upload(d_mm_start.p, mm_s);
+            launch(nullptr, 0);
             // Symbol hand-off at chunk boundaries. The M&M loop never re-merges bit for bit: its feedback is piecewise
             // constant through the 128-arm interpolator index rint(mu*128) (clock_recovery_mm.cpp:66), so independent
             // trajectories hover a fraction of an arm apart (tools/merge_study.py). What is certified is CONSISTENCY in
@@ -2297,7 +2325,7 @@ namespace sdhip
             verify_fix(
                 "mm", g.K,
                 [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_mm_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_mm_spec_c.p, d_mm_end_c.p, d_counts.p, MM_TOL, std::min(MM_TOL, MM_TOL_TIGHT),
+                    hipLaunchKernelGGL(k_mm_verdict, verdict_grid(g.K), dim3(256), 0, stream, g.K, d_mm_spec_c.p, d_mm_end_c.p, d_counts.p, MM_TOL, std::min(MM_TOL, MM_TOL_TIGHT),
                                        MM_TOL_OMEGA, d_skip.p, d_extra.p, vo, fails, force);
                 },
                 [&](const int *list, int nr) {
@@ -2315,45 +2343,21 @@ namespace sdhip
                             fprintf(stderr, "[sdhip] mm boundary %d rejected: dt %.5f samples = %.3f symbols, omega %.6f vs %.6f\n", idx[q], d, d / b.omega, a.omega, b.omega);
                         }
                     }
-                    hipLaunchKernelGGL(k_spec_from_prev<MmCert>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_mm_spec_c.p, d_mm_end_c.p);
-                    hipLaunchKernelGGL(k_spec_from_prev<MmState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_mm_spec.p, d_mm_end.p);
+                    spec_from_prev(list, nr, d_mm_spec_c.p, d_mm_end_c.p, d_mm_spec.p, d_mm_end.p);
                 },
-                [&](const int *redo, int nr) {
-                    launch_mm(A, symbuf.p, d_counts.p, g, mm_p, d_mm_start.p, d_mm_spec.p, d_mm_end.p, d_mm_spec_c.p, d_mm_end_c.p, redo, nr, stream, ckp,
-                              ck_per_chunk, (float)MM_TOL);
-                },
+                launch,
                 [&](int nf) {
-                    const long long wn = (std::min<long long>(2 * (long long)g.W, w_mm_cap) + 255) / 256 * 256;
+                    const long long wn = round_up(std::min<long long>(2 * (long long)g.W, w_mm_cap), 256);
                     if (cfg.warmup > 0 || getenv("SDHIP_W_MM") || wn <= (long long)g.W)
                         return false;
                     w_learned = wn;
                     if (getenv("SDHIP_DEBUG"))
                         fprintf(stderr, "[sdhip] mm     %d of %d boundaries outside the hand-off window: warm-up %d -> %lld samples\n", nf, g.K, g.W, w_learned);
                     mm_setup(w_learned);
-                    launch_mm(A, symbuf.p, d_counts.p, g, mm_p, d_mm_start.p, d_mm_spec.p, d_mm_end.p, d_mm_spec_c.p, d_mm_end_c.p, nullptr, 0, stream, ckp,
-                              ck_per_chunk, (float)MM_TOL);
+                    launch(nullptr, 0);
                     return true;
                 });
-            stats.chunks += g.K;
-            // compaction segments + offsets + total
-            SD_HIP(hipMemsetAsync(d_vout.p, 0, sizeof(VerdictOut), stream));
-            {
-                const int nt = (g.K + 1023) / 1024;
-                d_tile_sums.reserve(nt);
-                hipLaunchKernelGGL(k_chunk_scan_sums, dim3(nt), dim3(1024), 0, stream, g.K, 1, nullptr, d_counts.p, d_skip.p, d_extra.p, mm_p.cap, d_tile_sums.p,
-                                   d_vout.p);
-                hipLaunchKernelGGL(k_chunk_scan_apply, dim3(nt), dim3(1024), 0, stream, g.K, 1, nullptr, 1, nullptr, d_counts.p, d_skip.p, d_extra.p, d_tile_sums.p,
-                                   d_seg.p, d_offsets.p, d_vout.p);
-            }
-            SD_HIP(hipMemcpyAsync(h_vout.p, d_vout.p, sizeof(VerdictOut), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipMemcpyAsync(&mm_s, d_mm_end.p + (g.K - 1), sizeof(mm_s), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream));
-            mm_s.inc -= n; // clock_recovery_mm.cpp:123-126
-            if (mm_s.inc < 0)
-                mm_s.inc = 0;
-            if (h_vout.p->overflow)
-                throw HipError("symbol scratch overflow");
-            const long long tot = h_vout.p->total;
+            const long long tot = compact_scan(g.K, mm_p.cap, n, mm_s, d_mm_end.p);
             const long long need_soft = is_bpsk ? tot : 2 * tot;
             if ((size_t)need_soft > soft_cap)
                 throw HipError("soft output buffer too small");
@@ -2403,19 +2407,11 @@ namespace sdhip
                 SRC = reinterpret_cast<const cf32 *>(d_in);
             else
                 launch_convert(d_in, fmt, cfg.iq_swap, n, A, stream);
-            if (cfg.dc_block && cfg.exact)
+            if (cfg.dc_block)
             {
-                SD_HIP(hipMemcpyAsync(d_dc.p, &dc_s, sizeof(dc_s), hipMemcpyHostToDevice, stream));
-                launch_dcblock_seq(A, B, n, d_dc.p, stream);
-                SD_HIP(hipMemcpyAsync(&dc_s, d_dc.p, sizeof(dc_s), hipMemcpyDeviceToHost, stream));
+                dc_block(A, B, n, dc_s);
                 std::swap(A, B);
                 SRC = A; // the resampler reads the DC-blocked samples (found by the fuzz on the host twin: it read the stage's input)
-            }
-            else if (cfg.dc_block)
-            {
-                dc_block_chunked(A, B, n, dc_s);
-                std::swap(A, B);
-                SRC = A;
             }
             // ---- freq_shift (module_demod_base.cpp:122-123): the rotator, between the DC block and the resampler. The reference calls it once
             // per source buffer (the file source is built with the module's final d_buffer_size, module_demod_base.cpp:111; file_source.cpp:29)
@@ -2607,15 +2603,7 @@ namespace sdhip
             {
                 carrier_pll_chunked(A, B, n);
                 std::swap(A, B);
-                if (cfg.exact)
-                {
-                    SD_HIP(hipMemcpyAsync(d_dc.p, &dcc_s, sizeof(dcc_s), hipMemcpyHostToDevice, stream));
-                    launch_dcblock_seq(A, B, n, d_dc.p, stream);
-                    SD_HIP(hipMemcpyAsync(&dcc_s, d_dc.p, sizeof(dcc_s), hipMemcpyDeviceToHost, stream));
-                    SD_HIP(hipStreamSynchronize(stream));
-                }
-                else
-                    dc_block_chunked(A, B, n, dcc_s);
+                dc_block(A, B, n, dcc_s);
                 std::swap(A, B);
                 tick("carrier");
             }
@@ -2633,15 +2621,7 @@ namespace sdhip
             if (cfg.post_costas_dc)
             {
                 launch_derotate(A, n, cg, d_rot.p, order, stream);
-                if (cfg.exact)
-                {
-                    SD_HIP(hipMemcpyAsync(d_dc.p, &dc2_s, sizeof(dc2_s), hipMemcpyHostToDevice, stream));
-                    launch_dcblock_seq(A, B, n, d_dc.p, stream);
-                    SD_HIP(hipMemcpyAsync(&dc2_s, d_dc.p, sizeof(dc2_s), hipMemcpyDeviceToHost, stream));
-                    SD_HIP(hipStreamSynchronize(stream));
-                }
-                else
-                    dc_block_chunked(A, B, n, dc2_s);
+                dc_block(A, B, n, dc2_s);
                 std::swap(A, B);
                 mm_rot = nullptr;
             }
@@ -2859,37 +2839,22 @@ namespace sdhip
             d_dc_spec.reserve(g.K);
             d_dc_end.reserve(g.K);
             d_dc_starts.reserve(g.K);
-            std::vector<DcState> starts((size_t)g.K);
             if (g.K > 1)
             {
                 d_dc_partial.reserve((size_t)g.K);
                 launch_fdc_partial(in, g, d_dc_partial.p, stream);
-                std::vector<double> part((size_t)g.K);
-                SD_HIP(hipMemcpyAsync(part.data(), d_dc_partial.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-                SD_HIP(hipStreamSynchronize(stream));
-                const double beta = (double)(1.0f - 0.0001f);
-                double a = fdc_s.acc_re;
-                for (int k = 0; k < g.K; k++)
-                {
-                    starts[k] = DcState{(float)a, 0.0f};
-                    a = std::pow(beta, (double)(chunk_end(g, k) - chunk_begin(g, k))) * a + part[(size_t)k];
-                }
             }
-            starts[0] = fdc_s;
-            SD_HIP(hipMemcpyAsync(d_dc_starts.p, starts.data(), starts.size() * sizeof(DcState), hipMemcpyHostToDevice, stream));
-            launch_fdc(in, out, g, d_dc_starts.p, d_dc_spec.p, d_dc_end.p, nullptr, 0, stream);
+            std::vector<DcState> starts;
+            dc_scan_starts(g, fdc_s, 1, starts);
+            auto launch = [&](const int *redo, int nr) { launch_fdc(in, out, g, d_dc_starts.p, d_dc_spec.p, d_dc_end.p, redo, nr, stream); };
+            launch(nullptr, 0);
             verify_fix(
-                "fdc", g.K,
+                "fdc", g.K, d_dc_spec.p, d_dc_end.p,
                 [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_fdc_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_dc_spec.p, d_dc_end.p, 1e-5f, 1e-7f, vo, fails, force);
+                    hipLaunchKernelGGL(k_fdc_verdict, verdict_grid(g.K), dim3(256), 0, stream, g.K, d_dc_spec.p, d_dc_end.p, 1e-5f, 1e-7f, vo, fails, force);
                 },
-                [&](const int *list, int nr) {
-                    hipLaunchKernelGGL(k_spec_from_prev<DcState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_dc_spec.p, d_dc_end.p);
-                },
-                [&](const int *redo, int nr) { launch_fdc(in, out, g, d_dc_starts.p, d_dc_spec.p, d_dc_end.p, redo, nr, stream); });
-            stats.chunks += g.K;
-            SD_HIP(hipMemcpyAsync(&fdc_s, d_dc_end.p + (g.K - 1), sizeof(fdc_s), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream)); // (starts is a local)
+                launch);
+            fetch_last(fdc_s, d_dc_end.p, g.K); // (starts is a local)
         }
         // AGCBlock<float>(0.1, 0.5, 1, 65535): a lane per chunk warming up from gain 1. The gain's map per sample is g <- (1 - rate |x|) g + rate reference: at
         // rate 0.1 and a settled gain G it contracts by (1 - 0.05 / G) a sample, so 24 G / rate samples bring any start gain to the float floor.
@@ -2898,24 +2863,20 @@ namespace sdhip
             const int L = pick_L(n, ST_AGC);
             const double tau = std::max(1.0f, fagc_s.gain) / std::max(1e-6f, fagc_p.rate);
             long long W = cfg.exact ? 0 : (cfg.warmup > 0 ? cfg.warmup : (long long)(24.0 * tau));
-            W = (std::min<long long>(std::max<long long>(W, cfg.exact ? 0 : 256), 1 << 20) + 255) / 256 * 256;
+            W = round_up(std::min<long long>(std::max<long long>(W, cfg.exact ? 0 : 256), 1 << 20), 256);
             const ChunkGeom g = make_geom(n, L, (int)W);
             d_agc_spec.reserve(g.K);
             d_agc_end.reserve(g.K);
-            SD_HIP(hipMemcpyAsync(d_fagc_start.p, &fagc_s, sizeof(fagc_s), hipMemcpyHostToDevice, stream));
-            launch_fagc(in, out, g, fagc_p, d_fagc_start.p, d_agc_spec.p, d_agc_end.p, nullptr, 0, stream);
+            upload(d_fagc_start.p, fagc_s);
+            auto launch = [&](const int *redo, int nr) { launch_fagc(in, out, g, fagc_p, d_fagc_start.p, d_agc_spec.p, d_agc_end.p, redo, nr, stream); };
+            launch(nullptr, 0);
             verify_fix(
-                "fagc", g.K,
+                "fagc", g.K, d_agc_spec.p, d_agc_end.p,
                 [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_agc_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_agc_spec.p, d_agc_end.p, 1e-6f, vo, fails, force);
+                    hipLaunchKernelGGL(k_agc_verdict, verdict_grid(g.K), dim3(256), 0, stream, g.K, d_agc_spec.p, d_agc_end.p, 1e-6f, vo, fails, force);
                 },
-                [&](const int *list, int nr) {
-                    hipLaunchKernelGGL(k_spec_from_prev<AgcState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_agc_spec.p, d_agc_end.p);
-                },
-                [&](const int *redo, int nr) { launch_fagc(in, out, g, fagc_p, d_fagc_start.p, d_agc_spec.p, d_agc_end.p, redo, nr, stream); });
-            stats.chunks += g.K;
-            SD_HIP(hipMemcpyAsync(&fagc_s, d_agc_end.p + (g.K - 1), sizeof(fagc_s), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream));
+                launch);
+            fetch_last(fagc_s, d_agc_end.p, g.K);
         }
         // FIRBlock<float>: cur has FSK_HIST floats of room in front of it for the history
         void fsk_fir(float *cur, float *out, long long n)
@@ -2938,16 +2899,9 @@ namespace sdhip
             // tests/golden/fsk (level 0.16, gain_mu 1.7e-2) has boundaries outside the window behind 8 192 symbols of warm-up and none behind 16 384.
             if (!cfg.exact && n >= 4096)
             {
-                const long long m = std::min<long long>(n, 1 << 16);
-                launch_fmean_abs(cur, m, d_partial.p, stream);
-                double part[64];
-                SD_HIP(hipMemcpyAsync(part, d_partial.p, sizeof(part), hipMemcpyDeviceToHost, stream));
-                SD_HIP(hipStreamSynchronize(stream));
-                double sm = 0;
-                for (double v : part)
-                    sm += v;
-                if (std::isfinite(sm))
-                    fmm_level = std::min(1.0, std::max(0.05, sm / (double)m));
+                const double mean = head_mean_abs(cur, n);
+                if (std::isfinite(mean))
+                    fmm_level = std::min(1.0, std::max(0.05, mean));
             }
             const double gmu = std::max(1e-4f, cfg.clock_gain_mu) * fmm_level;
             fmm_p.fast_mult = 8.0f;
@@ -2956,11 +2910,8 @@ namespace sdhip
             const double w_full = 36.0 / gmu * sps, w_gear = (fmm_p.fast_syms + 16.0 / gmu) * sps;
             const long long w_cap = (long long)(64.0 / gmu * sps);
             long long W = cfg.exact ? 0 : (cfg.warmup > 0 ? cfg.warmup : (long long)std::min(w_full, std::max(w_gear, 0.5 * L)));
-            W = std::max(W, cfg.exact ? 0 : w_fmm_learned);
-            W = (W + 255) / 256 * 256;
-            // every lane runs W + L samples in sequence: with the chunk length left to the engine a chunk is at least half the warm-up (the lanes' work stays under 3 n)
-            if (!cfg.exact && cfg.chunk_len <= 0 && !getenv("SDHIP_CHUNK") && !getenv("SDHIP_CHUNK_MM"))
-                L = (int)std::min<long long>(std::max<long long>(L, (W / 2 + 63) / 64 * 64), 1 << 22);
+            W = round_up(std::max(W, cfg.exact ? 0 : w_fmm_learned), 256);
+            L = chunk_for_warmup(L, W, "SDHIP_CHUNK_MM");
             // Hand-off windows, samples of timing (SDHIP_FMM_TIGHT_MICRO / SDHIP_FMM_TOL_MICRO: experiments). TIGHT is the complex stage's (mm_stage). Its re-run window of
             // 5e-3 rests on a loop that is back on the floor a few hundred symbols into a chunk of thousands; this loop's time constant is 1 / level times as long
             // -- longer than a chunk --, so a boundary outside the tight window is re-run from the predecessor's exact state.
@@ -2984,7 +2935,7 @@ namespace sdhip
                 d_seg.reserve(2 * (size_t)g.K);
             };
             setup(W);
-            SD_HIP(hipMemcpyAsync(d_fmm_start.p, &fmm_s, sizeof(fmm_s), hipMemcpyHostToDevice, stream));
+            upload(d_fmm_start.p, fmm_s);
             auto launch = [&](const int *redo, int nr) {
                 launch_fmm(cur, d_frows.p, d_counts.p, g, fmm_p, d_fmm_start.p, d_fmm_spec.p, d_fmm_end.p, d_mm_spec_c.p, d_mm_end_c.p, redo, nr, stream);
             };
@@ -2992,16 +2943,12 @@ namespace sdhip
             verify_fix(
                 "fmm", g.K,
                 [&](VerdictOut *vo, int *fails, int force) {
-                    hipLaunchKernelGGL(k_mm_verdict, dim3((g.K + 255) / 256), dim3(256), 0, stream, g.K, d_mm_spec_c.p, d_mm_end_c.p, d_counts.p, TOL, TOL_TIGHT, TOL_OMEGA, d_skip.p,
+                    hipLaunchKernelGGL(k_mm_verdict, verdict_grid(g.K), dim3(256), 0, stream, g.K, d_mm_spec_c.p, d_mm_end_c.p, d_counts.p, TOL, TOL_TIGHT, TOL_OMEGA, d_skip.p,
                                        d_extra.p, vo, fails, force);
                 },
-                [&](const int *list, int nr) {
-                    hipLaunchKernelGGL(k_spec_from_prev<MmCert>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_mm_spec_c.p, d_mm_end_c.p);
-                    hipLaunchKernelGGL(k_spec_from_prev<FmmState>, dim3((nr + 255) / 256), dim3(256), 0, stream, list, nr, d_fmm_spec.p, d_fmm_end.p);
-                },
-                launch,
+                [&](const int *list, int nr) { spec_from_prev(list, nr, d_mm_spec_c.p, d_mm_end_c.p, d_fmm_spec.p, d_fmm_end.p); }, launch,
                 [&](int) { // many boundaries outside the tight window: the warm-up was too short for this signal's detector gain -- twice as long, and the stream keeps it
-                    const long long wn = (std::min<long long>(2 * (long long)g.W, w_cap) + 255) / 256 * 256;
+                    const long long wn = round_up(std::min<long long>(2 * (long long)g.W, w_cap), 256);
                     if (cfg.warmup > 0 || wn <= (long long)g.W)
                         return false;
                     w_fmm_learned = wn;
@@ -3009,24 +2956,7 @@ namespace sdhip
                     launch(nullptr, 0);
                     return true;
                 });
-            stats.chunks += g.K;
-            SD_HIP(hipMemsetAsync(d_vout.p, 0, sizeof(VerdictOut), stream));
-            {
-                const int nt = (g.K + 1023) / 1024;
-                d_tile_sums.reserve(nt);
-                hipLaunchKernelGGL(k_chunk_scan_sums, dim3(nt), dim3(1024), 0, stream, g.K, 1, nullptr, d_counts.p, d_skip.p, d_extra.p, fmm_p.cap, d_tile_sums.p, d_vout.p);
-                hipLaunchKernelGGL(k_chunk_scan_apply, dim3(nt), dim3(1024), 0, stream, g.K, 1, nullptr, 1, nullptr, d_counts.p, d_skip.p, d_extra.p, d_tile_sums.p, d_seg.p,
-                                   d_offsets.p, d_vout.p);
-            }
-            SD_HIP(hipMemcpyAsync(h_vout.p, d_vout.p, sizeof(VerdictOut), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipMemcpyAsync(&fmm_s, d_fmm_end.p + (g.K - 1), sizeof(fmm_s), hipMemcpyDeviceToHost, stream));
-            SD_HIP(hipStreamSynchronize(stream));
-            fmm_s.inc -= n; // clock_recovery_mm.cpp:123-126
-            if (fmm_s.inc < 0)
-                fmm_s.inc = 0;
-            if (h_vout.p->overflow)
-                throw HipError("symbol scratch overflow");
-            const long long tot = h_vout.p->total;
+            const long long tot = compact_scan(g.K, fmm_p.cap, n, fmm_s, d_fmm_end.p);
             if ((size_t)tot > soft_cap)
                 throw HipError("soft output buffer too small");
             if (d_syms && (size_t)tot > syms_cap)
