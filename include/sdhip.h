@@ -662,6 +662,84 @@ extern "C"
     int64_t sdhip_lrpt_process_dev(void *h, const int8_t *d_soft, size_t n, uint8_t *d_cadu, size_t cap_frames);
     int sdhip_lrpt_get_stats(void *h, sdhip_lrpt_stats *st);
 
+    /* ---- "ccsds_ldpc_decoder", "ldpc_rate": "7/8" (ccsds_ldpc.h) ----------------------------------------------------------------------------------
+       CCSDSLDPCDecoderModule::process() (src-core/pipeline/modules/ccsds/module_ccsds_ldpc_decoder.cpp:134-277): soft symbols in reads of 8192 bytes ->
+       CorrelatorGeneric on the 32-bit ASM (src-core/common/codings/generic_correlator.cpp:7-64, 176-264; a read that finds the ASM at pos != 0 is slid by
+       pos and keeps the phase / swap of its first window) -> rotate_soft (rotation.cpp:4-58), for OQPSK with swap the module's Q shift (:163-172) ->
+       derand_ccsds_soft (randomization.cpp:80-88) -> CCSDSLDPC::decode (ldpc/ccsds_ldpc.cpp:76-123) over LDPCDecoderGeneric (ldpc/ldpc_decoder_generic.cpp:69-194:
+       the build without the simd_extensions plugin, one frame per call) -> the direct branch (:245-268: 1D FC CF 1A + 1020 repacked bytes) or, with
+       internal_stream, the first 7136 bits of every codeword through deframing::BPSK_CCSDS_Deframer (:233-242) -> CADUs of internal_cadu_size / 8 bytes.
+       Refused with a message (such runs stay on the CPU module): the AR4JA rates 1/2, 2/3, 4/5; internal_cadu_size % 8 != 0 (padded CADUs). "ldpc2" and
+       "hip_devices" have no field here: the plugin keeps the CPU module for them. */
+    enum
+    {
+        SDHIP_CCSDS_LDPC_RATE_1_2 = 0, /* codings::ldpc::ldpc_rate_t, ldpc/ccsds_ldpc.h:10-16 */
+        SDHIP_CCSDS_LDPC_RATE_2_3 = 1,
+        SDHIP_CCSDS_LDPC_RATE_4_5 = 2,
+        SDHIP_CCSDS_LDPC_RATE_7_8 = 3
+    };
+    typedef struct sdhip_ccsds_ldpc_cfg
+    {
+        int constellation;      /* "constellation": SDHIP_BPSK / SDHIP_QPSK / SDHIP_OQPSK (mandatory) */
+        int rate;               /* "ldpc_rate": SDHIP_CCSDS_LDPC_RATE_* (mandatory) */
+        int block_size;         /* "ldpc_block_size", default 0 (read by the AR4JA rates only) */
+        int iterations;         /* "ldpc_iterations" (mandatory) */
+        int derandomize;        /* "derandomize", default 1 */
+        int internal_stream;    /* "internal_stream", default 0 */
+        int internal_cadu_size; /* "internal_cadu_size" in BITS incl. ASM (with internal_stream) */
+        uint32_t internal_asm;  /* "internal_asm", default 0x1ACFFC1D */
+        int device;
+    } sdhip_ccsds_ldpc_cfg;
+    typedef struct sdhip_ccsds_ldpc_stats
+    {
+        uint64_t soft_in;      /* soft bytes consumed */
+        uint64_t frames_seen;  /* codewords decoded */
+        uint64_t frames_out;   /* frames / CADUs written */
+        int correlator_lock;   /* "correlator_lock": the last read found the ASM at position 0 */
+        float correlator_corr; /* "correlator_corr" */
+        int ldpc_corr;         /* "ldpc_corr": CCSDSLDPC::decode's return value for the last codeword */
+        int deframer_state;    /* internal_stream: 2 NOSYNC, 6 SYNCING, 12 SYNCED ("deframer_lock" = SYNCED) */
+        uint32_t chain_rounds; /* speculation rounds of the frame chain (one per slide) */
+        uint32_t chain_serial; /* calls that fell back to the serial walk */
+    } sdhip_ccsds_ldpc_stats;
+    typedef struct sdhip_ccsds_ldpc_desc
+    {
+        uint64_t offset; /* stream position of the frame's first soft byte */
+        int sync;        /* CorrelatorGeneric's best_sync (generic_correlator.cpp:233-261 maps it to phase / swap) */
+        float cor;       /* its correlation */
+        int corrections; /* CCSDSLDPC::decode's return value */
+        int locked;      /* the read found it at position 0 */
+    } sdhip_ccsds_ldpc_desc;
+    void sdhip_ccsds_ldpc_cfg_default(sdhip_ccsds_ldpc_cfg *cfg);
+    void *sdhip_ccsds_ldpc_create(const sdhip_ccsds_ldpc_cfg *cfg); /* NULL on error */
+    void sdhip_ccsds_ldpc_destroy(void *h);
+    int sdhip_ccsds_ldpc_frame_bytes(void *h); /* 1024 (direct) or internal_cadu_size / 8 */
+    /* Host-buffer path: append n soft bytes; every complete read is decoded, an incomplete one (an incomplete slide included) stays pending. */
+    int sdhip_ccsds_ldpc_push(void *h, const int8_t *soft, size_t n);
+    int64_t sdhip_ccsds_ldpc_pull(void *h, uint8_t *frames, size_t cap_frames);
+    /* Device-resident path: n more soft bytes in HBM -> frames in d_frames (device). Returns the frames written, < 0 on error. The output does not depend on
+       how the stream is cut into calls. internal_stream: a CADU leaves with the call that decodes its last bit. */
+    int64_t sdhip_ccsds_ldpc_process_dev(void *h, const int8_t *d_soft, size_t n, uint8_t *d_frames, size_t cap_frames);
+    int sdhip_ccsds_ldpc_get_stats(void *h, sdhip_ccsds_ldpc_stats *st);
+    /* the frames the last push / process_dev call decoded (host table). Returns their number, which may exceed cap. */
+    int64_t sdhip_ccsds_ldpc_get_descs(void *h, sdhip_ccsds_ldpc_desc *out, size_t cap);
+    /* CorrelatorGeneric's syncword tables as its constructor builds them (generic_correlator.cpp:7-64): out128 = 4 x 32 floats. Returns their number (2 / 4). */
+    int sdhip_ccsds_ldpc_syncwords(int constellation, float *out128);
+    /* the decoder's schedule: rows per dependency level of one iteration (computed from the row list at create). Returns the number of levels. */
+    int sdhip_ccsds_ldpc_levels(void *h, int *sizes, int cap);
+    /* the rows in the order the kernel runs them, level after level (sizes: sdhip_ccsds_ldpc_levels). Returns the number of rows. */
+    int sdhip_ccsds_ldpc_schedule(void *h, uint16_t *rows, int cap);
+    /* unit entries. LDPCDecoderGeneric::decode behind CCSDSLDPC::decode's placement (ldpc/ccsds_ldpc.cpp:78-86, ldpc/ldpc_decoder_generic.cpp:69-194): nframes
+       prepared codewords of 8160 soft bytes (device) -> d_bits, 8160 bytes per frame, one bit per byte (the last two 0), d_corrections[nframes] (device). */
+    int sdhip_op_ccsds_ldpc_decode(int device, int rate, int iterations, const int8_t *d_codewords, int nframes, uint8_t *d_bits, int *d_corrections);
+    /* LDPCDecoderGeneric::decode (ldpc/ldpc_decoder_generic.cpp:69-194) for ANY parity check matrix the kernel holds (<= 1022 rows of <= 32 edges, <= 8176 columns):
+       rows (HOST) = ncn x 32 column indices, 0xFFFF = no edge; nwords words of nvn soft bytes (device) -> d_bits, nvn bytes a word, one bit per byte, and
+       d_corrections[nwords] (device). The level schedule is computed from the rows, as at create. */
+    int sdhip_op_ldpc_generic_decode(int device, const uint16_t *rows, int ncn, int nvn, int iterations, const int8_t *d_words, int nwords, uint8_t *d_bits, int *d_corrections);
+    /* CorrelatorGeneric::correlate's inner loop per position (generic_correlator.cpp:178, 211-226): for p < n - 31 the greatest of the syncword correlations
+       at p that is > 0 (else 0) and the first syncword reaching it. d_cor / d_sync: n - 31 entries (device). Returns n - 31, < 0 on error. */
+    int64_t sdhip_op_generic_correlate(int device, int constellation, const int8_t *d_soft, size_t n, float *d_cor, uint8_t *d_sync);
+
     /* ---- misc ------------------------------------------------------------------------ */
     const char *sdhip_last_error(void);
     const char *sdhip_version(void);

@@ -1747,6 +1747,137 @@ namespace sdhip_plugin
         }
     };
 
+    // ------------------------------------------------------------------------------------------------ ccsds_ldpc_decoder
+    // CCSDSLDPCDecoderModule (src-core/pipeline/modules/ccsds/module_ccsds_ldpc_decoder.{h,cpp}) at "ldpc_rate": "7/8" on sdhip_ccsds_ldpc_* (csrc/ccsds_ldpc.h):
+    // same keys, .soft file / fifo in, .cadu (or .frm with "ccsds": false) out, the module's statistics keys. The AR4JA rates, "ldpc2", padded CADUs
+    // (internal_cadu_size % 8 != 0) and "hip_devices" stay on the CPU module.
+    class CCSDSLDPCDecoderHipModule : public base::FileStreamToFileStreamModule
+    {
+        sdhip_ccsds_ldpc_cfg cfg;
+        void *h = nullptr;
+        std::atomic<float> correlator_cor{0};
+        std::atomic<int> locked{0}, ldpc_corr{0}, deframer_state{2};
+        uint64_t file_bytes = 0, file_pos = 0;
+
+    public:
+        CCSDSLDPCDecoderHipModule(std::string input_file, std::string output_file_hint, nlohmann::json parameters)
+            : base::FileStreamToFileStreamModule(input_file, output_file_hint, parameters)
+        {
+            std::string why;
+            if (!covers(parameters, why))
+                throw satdump_exception("ccsds_ldpc_decoder_hip: " + why);
+            sdhip_ccsds_ldpc_cfg_default(&cfg);
+            cfg.constellation = constellation_of(parameters["constellation"].get<std::string>(), true);
+            cfg.rate = SDHIP_CCSDS_LDPC_RATE_7_8;
+            opt(parameters, "ldpc_block_size", cfg.block_size);
+            cfg.iterations = parameters["ldpc_iterations"].get<int>();
+            bool derand = true, internal = false, is_ccsds = true;
+            opt(parameters, "derandomize", derand);
+            opt(parameters, "internal_stream", internal);
+            opt(parameters, "ccsds", is_ccsds);
+            cfg.derandomize = derand ? 1 : 0;
+            cfg.internal_stream = internal ? 1 : 0;
+            if (parameters.count("internal_stream") > 0) // module_ccsds_ldpc_decoder.cpp:34
+                cfg.internal_cadu_size = parameters["internal_cadu_size"].get<int>();
+            if (internal && parameters.count("internal_asm") > 0)
+                cfg.internal_asm = (uint32_t)std::stoul(parameters["internal_asm"].get<std::string>(), nullptr, 16);
+            opt(parameters, "hip_device", cfg.device);
+            fsfsm_file_ext = is_ccsds ? ".cadu" : ".frm";
+        }
+        ~CCSDSLDPCDecoderHipModule()
+        {
+            if (h)
+                sdhip_ccsds_ldpc_destroy(h);
+        }
+        static bool covers(const nlohmann::json &p, std::string &why)
+        {
+            if (p.count("ldpc_rate") == 0 || p["ldpc_rate"].get<std::string>() != "7/8")
+                why = "only ldpc_rate 7/8 runs on the device";
+            else if (p.count("ldpc2") > 0 && p["ldpc2"].get<bool>())
+                why = "ldpc2 (the labrador decoder) is the CPU module's";
+            else if (p.count("constellation") == 0 || (p["constellation"].get<std::string>() != "bpsk" && p["constellation"].get<std::string>() != "qpsk" &&
+                                                       p["constellation"].get<std::string>() != "oqpsk"))
+                why = "constellation";
+            else if (p.count("internal_stream") > 0 && p["internal_stream"].get<bool>() && p.count("internal_cadu_size") > 0 && p["internal_cadu_size"].get<int>() % 8 != 0)
+                why = "padded CADUs (internal_cadu_size % 8 != 0)";
+            else if (p.count("hip_devices") > 0)
+                why = "hip_devices: the LDPC decoder is not sharded";
+            else
+                return true;
+            return false;
+        }
+        void init()
+        {
+            base::FileStreamToFileStreamModule::init();
+            h = sdhip_ccsds_ldpc_create(&cfg);
+            if (!h)
+                throw satdump_exception(std::string("ccsds_ldpc_decoder_hip: ") + sdhip_last_error());
+            if (input_data_type == DATA_FILE)
+                file_bytes = (uint64_t)std::filesystem::file_size(d_input_file);
+        }
+        void process()
+        {
+            // the module reads one frame (8192 soft bytes) per iteration, plus the correlator's slide; here a file goes to the device in batches of 1024 frames'
+            // worth, a fifo frame by frame. An incomplete last read is dropped, as the module's loop ends on it.
+            const size_t chunk = (size_t)8192 * (input_data_type == DATA_FILE ? 1024 : 1);
+            const size_t fb = (size_t)sdhip_ccsds_ldpc_frame_bytes(h);
+            std::vector<int8_t> soft(chunk);
+            std::vector<uint8_t> frames(fb * 1100);
+            while (should_run())
+            {
+                size_t got = chunk;
+                if (input_data_type == DATA_FILE)
+                {
+                    got = (size_t)std::min<uint64_t>(chunk, file_bytes > file_pos ? file_bytes - file_pos : 0);
+                    file_pos += got;
+                }
+                read_data((uint8_t *)soft.data(), chunk);
+                if (got == 0)
+                    break;
+                if (sdhip_ccsds_ldpc_push(h, soft.data(), got) < 0)
+                    throw satdump_exception(std::string("ccsds_ldpc_decoder_hip: ") + sdhip_last_error());
+                for (;;)
+                {
+                    const int64_t n = sdhip_ccsds_ldpc_pull(h, frames.data(), frames.size() / fb);
+                    if (n < 0)
+                        throw satdump_exception(std::string("ccsds_ldpc_decoder_hip: ") + sdhip_last_error());
+                    if (n == 0)
+                        break;
+                    write_data(frames.data(), (size_t)n * fb);
+                }
+                sdhip_ccsds_ldpc_stats st;
+                sdhip_ccsds_ldpc_get_stats(h, &st);
+                locked = st.correlator_lock;
+                correlator_cor = st.correlator_corr;
+                ldpc_corr = st.ldpc_corr;
+                deframer_state = st.deframer_state;
+            }
+            cleanup();
+        }
+        void drawUI(bool) {}
+        nlohmann::json getModuleStats()
+        { // module_ccsds_ldpc_decoder.cpp:279-295
+            auto v = base::FileStreamToFileStreamModule::getModuleStats();
+            const int ds = deframer_state.load();
+            if (cfg.internal_stream)
+                v["deframer_lock"] = ds == 12;
+            v["correlator_lock"] = locked.load() != 0;
+            v["correlator_corr"] = correlator_cor.load();
+            v["ldpc_corr"] = ldpc_corr.load();
+            v["lock_state"] = locked.load() ? "SYNCED" : "NOSYNC";
+            if (cfg.internal_stream)
+                v["deframer_state"] = ds == 2 ? "NOSYNC" : (ds == 6 ? "SYNCING" : "SYNCED");
+            return v;
+        }
+        static std::string getID() { return "ccsds_ldpc_decoder_hip"; }
+        virtual std::string getIDM() { return getID(); }
+        static nlohmann::json getParams() { return {}; }
+        static std::shared_ptr<ProcessingModule> getInstance(std::string input_file, std::string output_file_hint, nlohmann::json parameters)
+        {
+            return std::make_shared<CCSDSLDPCDecoderHipModule>(input_file, output_file_hint, parameters);
+        }
+    };
+
     // ------------------------------------------------------------------------------------------------ dvbs2_ts_extractor
     // S2TStoTCPModule (plugins/dvb_support/dvbs2/module_s2_ts_extractor.{h,cpp}) on sdhip_s2_ts_* (csrc/dvbs2_ts.hip): same keys ("bb_size", or "modcod" mandatory +
     // "shortframes" / "pilots" -> BBFrameBCH::dataSize(), :24-52, the same exception text), .bbframe file or fifo in, one BBFrameTSParser::work call per frame's
@@ -2169,6 +2300,7 @@ namespace sdhip_plugin
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, METEORLRPTM2XHipModule);
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, FengyunAHRPTDecoderHipModule);
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, FengyunMPTDecoderHipModule);
+            REGISTER_MODULE_EXTERNAL(evt.modules_registry, CCSDSLDPCDecoderHipModule);
         }
         static void startedHandler(const satdump::SatDumpStartedEvent &)
         {
@@ -2252,6 +2384,19 @@ namespace sdhip_plugin
                         if (!METEORLRPTDecoderHipModule::covers(p))
                             return cpu(in, out, p);
                         return METEORLRPTDecoderHipModule::getInstance(in, out, p);
+                    };
+                }
+                else if (e.id == "ccsds_ldpc_decoder")
+                { // rate 7/8 only; the AR4JA rates, ldpc2, padded CADUs and hip_devices stay on the CPU module
+                    auto cpu = e.inst;
+                    e.inst = [cpu](std::string in, std::string out, nlohmann::json p) -> std::shared_ptr<ProcessingModule> {
+                        std::string why;
+                        if (!CCSDSLDPCDecoderHipModule::covers(p, why))
+                        {
+                            logger->info("sdhip_support: ccsds_ldpc_decoder stays on the CPU module for this run (" + why + ")");
+                            return cpu(in, out, p);
+                        }
+                        return CCSDSLDPCDecoderHipModule::getInstance(in, out, p);
                     };
                 }
                 else if (e.id == "ccsds_simple_psk_decoder")

@@ -111,6 +111,24 @@ class LrptStats(C.Structure):
                 ("cor", C.c_int), ("rs_errors", C.c_int * 4)]
 
 
+class CcsdsLdpcCfg(C.Structure):
+    """sdhip_ccsds_ldpc_cfg (include/sdhip.h): the JSON keys of ccsds_ldpc_decoder."""
+    _fields_ = [("constellation", C.c_int), ("rate", C.c_int), ("block_size", C.c_int), ("iterations", C.c_int), ("derandomize", C.c_int),
+                ("internal_stream", C.c_int), ("internal_cadu_size", C.c_int), ("internal_asm", C.c_uint32), ("device", C.c_int)]
+
+
+class CcsdsLdpcStats(C.Structure):
+    _fields_ = [("soft_in", C.c_uint64), ("frames_seen", C.c_uint64), ("frames_out", C.c_uint64), ("correlator_lock", C.c_int), ("correlator_corr", C.c_float),
+                ("ldpc_corr", C.c_int), ("deframer_state", C.c_int), ("chain_rounds", C.c_uint32), ("chain_serial", C.c_uint32)]
+
+
+class CcsdsLdpcDesc(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("sync", C.c_int), ("cor", C.c_float), ("corrections", C.c_int), ("locked", C.c_int)]
+
+
+# codings::ldpc::ldpc_rate_t (common/codings/ldpc/ccsds_ldpc.h:10-16)
+CCSDS_LDPC_RATES = {"1/2": 0, "2/3": 1, "4/5": 2, "7/8": 3}
+
 # dvbs2_code_rate_t (common/codings/dvb-s2/dvbs2.h:9-23)
 S2_RATES = {"1/4": 0, "1/3": 1, "2/5": 2, "1/2": 3, "3/5": 4, "2/3": 5, "3/4": 6, "4/5": 7, "5/6": 8, "7/8": 9, "8/9": 10, "9/10": 11}
 
@@ -268,6 +286,27 @@ def lib():
             L.sdhip_lrpt_process_dev.restype = C.c_int64
             L.sdhip_lrpt_process_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
             L.sdhip_lrpt_get_stats.argtypes = [C.c_void_p, C.POINTER(LrptStats)]
+        if hasattr(L, "sdhip_ccsds_ldpc_create"):
+            L.sdhip_ccsds_ldpc_cfg_default.argtypes = [C.POINTER(CcsdsLdpcCfg)]
+            L.sdhip_ccsds_ldpc_create.restype = C.c_void_p
+            L.sdhip_ccsds_ldpc_create.argtypes = [C.POINTER(CcsdsLdpcCfg)]
+            L.sdhip_ccsds_ldpc_destroy.argtypes = [C.c_void_p]
+            L.sdhip_ccsds_ldpc_frame_bytes.argtypes = [C.c_void_p]
+            L.sdhip_ccsds_ldpc_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.sdhip_ccsds_ldpc_pull.restype = C.c_int64
+            L.sdhip_ccsds_ldpc_pull.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.sdhip_ccsds_ldpc_process_dev.restype = C.c_int64
+            L.sdhip_ccsds_ldpc_process_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+            L.sdhip_ccsds_ldpc_get_stats.argtypes = [C.c_void_p, C.POINTER(CcsdsLdpcStats)]
+            L.sdhip_ccsds_ldpc_get_descs.restype = C.c_int64
+            L.sdhip_ccsds_ldpc_get_descs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.sdhip_ccsds_ldpc_syncwords.argtypes = [C.c_int, C.c_void_p]
+            L.sdhip_ccsds_ldpc_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.sdhip_ccsds_ldpc_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.sdhip_op_ccsds_ldpc_decode.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            L.sdhip_op_ldpc_generic_decode.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            L.sdhip_op_generic_correlate.restype = C.c_int64
+            L.sdhip_op_generic_correlate.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.sdhip_prof_enable.argtypes = [C.c_int]
         L.sdhip_pool_enable.argtypes = [C.c_int]
         L.sdhip_prof_get.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
@@ -546,3 +585,77 @@ class BchDecoder:
     def pack_dev(self, d_soft_ptr, soft_stride, nframes, d_out_ptr, out_stride):
         if lib().sdhip_s2_pack_dev(self.h, d_soft_ptr, soft_stride, nframes, d_out_ptr, out_stride) < 0:
             raise SdhipError(lib().sdhip_last_error().decode())
+
+
+def ccsds_ldpc_cfg(**kw) -> CcsdsLdpcCfg:
+    """sdhip_ccsds_ldpc_cfg_default plus the given keys; constellation and rate may be the JSON strings, internal_asm the JSON hex string."""
+    c = CcsdsLdpcCfg()
+    lib().sdhip_ccsds_ldpc_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        if k == "constellation" and isinstance(v, str):
+            v = CONSTELLATIONS[v]
+        if k == "rate" and isinstance(v, str):
+            v = CCSDS_LDPC_RATES[v]
+        if k == "internal_asm" and isinstance(v, str):
+            v = int(v, 16)
+        setattr(c, k, v)
+    return c
+
+
+class CcsdsLdpc:
+    """ccsds_ldpc_decoder ("ldpc_rate": "7/8") on one GPU stream (include/sdhip.h, sdhip_ccsds_ldpc_*): soft bytes in, frames / CADUs out."""
+
+    def __init__(self, cfg: CcsdsLdpcCfg):
+        self.cfg = cfg
+        self.h = lib().sdhip_ccsds_ldpc_create(C.byref(cfg))
+        if not self.h:
+            raise SdhipError(f"sdhip_ccsds_ldpc_create failed: {last_error()}")
+        self.frame_bytes = lib().sdhip_ccsds_ldpc_frame_bytes(self.h)
+
+    def close(self):
+        if self.h:
+            lib().sdhip_ccsds_ldpc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, soft: np.ndarray):
+        soft = np.ascontiguousarray(soft, dtype=np.int8)
+        _check(lib().sdhip_ccsds_ldpc_push(self.h, soft.ctypes.data_as(C.c_void_p), soft.size), "sdhip_ccsds_ldpc_push")
+
+    def pull(self, max_frames: int = 1 << 16) -> np.ndarray:
+        out = np.empty((max_frames, self.frame_bytes), dtype=np.uint8)
+        n = _check(lib().sdhip_ccsds_ldpc_pull(self.h, out.ctypes.data_as(C.c_void_p), max_frames), "sdhip_ccsds_ldpc_pull")
+        return out[:n].copy()
+
+    def process_dev(self, d_soft_ptr: int, n: int, d_frames_ptr: int, cap_frames: int) -> int:
+        return _check(lib().sdhip_ccsds_ldpc_process_dev(self.h, d_soft_ptr, n, d_frames_ptr, cap_frames), "sdhip_ccsds_ldpc_process_dev")
+
+    def stats(self) -> CcsdsLdpcStats:
+        st = CcsdsLdpcStats()
+        lib().sdhip_ccsds_ldpc_get_stats(self.h, C.byref(st))
+        return st
+
+    def descs(self) -> np.ndarray:
+        """the frames of the last push / process_dev call: a structured array (offset, sync, cor, corrections, locked)"""
+        dt = np.dtype([("offset", np.uint64), ("sync", np.int32), ("cor", np.float32), ("corrections", np.int32), ("locked", np.int32)])
+        n = lib().sdhip_ccsds_ldpc_get_descs(self.h, None, 0)
+        out = np.zeros(n, dtype=dt)
+        if n:
+            lib().sdhip_ccsds_ldpc_get_descs(self.h, out.ctypes.data_as(C.c_void_p), n)
+        return out
+
+    def levels(self) -> list:
+        buf = (C.c_int * 64)()
+        n = lib().sdhip_ccsds_ldpc_levels(self.h, buf, 64)
+        return list(buf[:n])
+
+    def schedule(self) -> np.ndarray:
+        """the rows in the order the decoder kernel runs them (level after level: levels())"""
+        out = np.zeros(lib().sdhip_ccsds_ldpc_schedule(self.h, None, 0), dtype=np.uint16)
+        lib().sdhip_ccsds_ldpc_schedule(self.h, out.ctypes.data_as(C.c_void_p), len(out))
+        return out

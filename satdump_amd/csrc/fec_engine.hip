@@ -432,7 +432,9 @@ namespace sdhip
         std::vector<FrameDesc> h_frames;
         std::vector<int> h_dst;
 
-        explicit FecEngine(const sdhip_fec_cfg &c) : cfg(c)
+        // simple_block_bits > 0 (ccsds_simple_psk_decoder only; ccsds_ldpc.h's deframer): the block the handle works in, in place of the module's read of cadu_size
+        // soft bytes. The deframer is bit-serial, so the frames are the same; what changes is how many bits may wait for a block to fill.
+        explicit FecEngine(const sdhip_fec_cfg &c, int simple_block_bits = 0) : cfg(c)
         {
             SD_HIP(hipSetDevice(cfg.device));
             // Neither stream takes part in the legacy default stream's implicit ordering: a forward pass must not wait for (or hold up) whatever else the
@@ -561,7 +563,7 @@ namespace sdhip
                     throw HipError("CCSDS Simple PSK Decoder : invalid Reed-Solomon type!");
                 if (cfg.rs_i < 0 || cfg.rs_i > 8)
                     throw HipError("rs_i out of range");
-                B = F = cfg.cadu_size;
+                B = F = simple_block_bits > 0 ? simple_block_bits : cfg.cadu_size;
                 st_synced = 12;
                 hard.qpsk = cfg.constellation == SDHIP_QPSK;
                 hard.nrzm = cfg.nrzm;
@@ -2850,6 +2852,14 @@ extern "C"
         c->qpsk_swap_diff = 1;
     }
 
+    void *sdhip_fec_create_bit_deframer(const sdhip_fec_cfg *cfg, int block_bits)
+    { // library-internal (fec_kernels.h): see FecEngine's constructor
+        SD_GUARD_BEGIN
+        if (cfg->decoder != SDHIP_DEC_SIMPLE_PSK || block_bits <= 0 || block_bits % 32 != 0)
+            throw HipError("bit deframer: a ccsds_simple_psk_decoder configuration and a block of whole 32-bit words");
+        return new FecEngine(*cfg, block_bits);
+        SD_GUARD_END(nullptr)
+    }
     void *sdhip_fec_create(const sdhip_fec_cfg *cfg)
     {
         SD_GUARD_BEGIN

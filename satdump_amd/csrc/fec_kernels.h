@@ -239,3 +239,8 @@ namespace sdhip
     void viterbi27_frames(int frame_bits, int ber_test_size, const int8_t *d_soft, int nframes, int start_in0, uint8_t *d_out, std::vector<int> *ber_err, int *ret_state,
                           unsigned *enc_state = nullptr);
 } // namespace sdhip
+
+// fec_engine.hip, library-internal: a ccsds_simple_psk_decoder handle (the sdhip_fec_* functions serve it) that works in blocks of block_bits soft bytes instead of
+// cadu_size -- the engine's ASM deframer for a caller whose bits arrive in units of its own (ccsds_ldpc.h: 7136 decoded bits a codeword). NULL on error.
+struct sdhip_fec_cfg;
+extern "C" void *sdhip_fec_create_bit_deframer(const struct sdhip_fec_cfg *cfg, int block_bits);

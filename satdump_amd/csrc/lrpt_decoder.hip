@@ -653,3 +653,6 @@ extern "C"
         SD_GUARD_END(-1)
     }
 }
+
+// ccsds_ldpc_decoder ("ldpc_rate": "7/8"): kernels, engine and C ABI
+#include "ccsds_ldpc.h"
