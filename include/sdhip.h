@@ -353,7 +353,10 @@ extern "C"
        frame_bits/8 bytes, ber_out (host, may be NULL) = Viterbi27::ber() after each call. CCSDS polys {79, 109} only; soft input only. */
     int sdhip_op_viterbi27(int device, int frame_bits, int ber_test_size, const int8_t *d_soft, int nframes, uint8_t *d_out, float *ber_out);
     /* reedsolomon::ReedSolomon::decode_interlaved over nframes (reedsolomon.cpp:53-116). d_data points at
-       the first codeblock byte of frame 0 (cadu+4); errors: nframes*I ints (device). fill_bytes as in the reference. */
+       the first codeblock byte of frame 0 (cadu+4) of frames frame_stride >= 4 + (255 - max(fill_bytes, 0)) * I bytes apart; errors: nframes*I
+       ints (device). fill_bytes as in the reference, its -1 included: where the frame is longer than its codeblock, the byte the 256-byte interleave
+       leaves at offset 4 + 255 * I + b of the frame after a successful decode of codeword b is written too (frames are taken one by one: nothing
+       is written into a successor). I = 1..8. */
     int sdhip_op_rs_decode(int device, uint8_t *d_data, int nframes, int frame_stride, int dualbasis, int I, int rs_type, int fill_bytes, int *d_errors);
     /* dsp blocks over one stream, EXACT sequential semantics (single lane), for arithmetic parity:
        kind 0 AGC(rate,ref,gain,max) agc.cpp:25-39 | 1 RRC FIR(fs,symrate,alpha,ntaps) fir.cpp:74-83 |

@@ -377,6 +377,8 @@ namespace sdhip
 
         // RS bookkeeping
         int last_errors[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int rs_tail = 0;       // bytes the interleaved codeblock reaches behind a CADU (FrameCfg::rs_tail)
+        int rs_slots_used = 0; // most frames one deframer call has returned so far = slots of the reference's frame buffer that hold a frame (FRAME_NEXT_SLOT_USED)
 
         // pending partial block (host copy) and output queue for the host path
         std::vector<int8_t> pending;
@@ -623,8 +625,20 @@ namespace sdhip
                     throw HipError("CCSDS Concatenated 1/2 Decoder : invalid Reed-Solomon type!");
                 if (cfg.rs_i < 0 || cfg.rs_i > 8)
                     throw HipError("rs_i out of range");
-                if (cfg.rs_i != 0 && 4 + 255 * cfg.rs_i - std::max(cfg.rs_fill_bytes, 0) * cfg.rs_i > cadu_bytes + 0 && cfg.rs_fill_bytes >= 0 && false)
-                    throw HipError("RS block does not fit the CADU");
+            }
+            if (cfg.rs_i != 0)
+            { // the RS tail's parity contract: what ReedSolomon::decode_interlaved reads and writes behind a frame
+                if (cfg.rs_fill_bytes < -1 || cfg.rs_fill_bytes >= 255 - (cfg.rs_type == SDHIP_RS239 ? 16 : 32)) // (a shortened code keeps a message byte)
+                    throw HipError("rs_fill_bytes out of range");
+                rs_tail = std::max(0, 4 + (255 - std::max(cfg.rs_fill_bytes, 0)) * cfg.rs_i - cadu_bytes);
+                if (rs_tail > 4)
+                    throw HipError("RS block does not fit the CADU: the interleaved codeblock ends more than 4 bytes behind the frame, where the reference decodes "
+                                   "whatever its frame buffer holds");
+                // one deframer returns two frames from one call only if a CADU is shorter than the call's bits (two windows a call at most on the punctured path)
+                const bool two_per_call = cfg.cadu_size < (punc.rate != 0 ? 2 * F : F);
+                if (cfg.rs_fill_bytes == -1 && two_per_call && 4 + 255 * cfg.rs_i + (cfg.rs_i - 1) >= cadu_bytes + 4)
+                    throw HipError("rs_fill_bytes = -1: the RS overrun byte (offset 4 + 255 * rs_i + b of a frame) would land in the data of the next frame of the same "
+                                   "deframer call, which the reference then decodes changed; the parallel tail does not reproduce that");
             }
             vc.B = B;
             vc.F = F;
@@ -1058,7 +1072,7 @@ namespace sdhip
                     for (int f = 0; f < nf; f++)
                         collect->done_blk[f] = (base_abs + W.frames[f].pos + (cfg.cadu_size - 32) - 1) / F;
                 }
-                if (nf > 1 && cfg.rs_i != 0 && cfg.rs_fill_bytes == -1)
+                if (nf > 0 && cfg.rs_i != 0 && (cfg.rs_fill_bytes == -1 || rs_tail > 0))
                 { // frames the reference's deframer returned from ONE work() call (one Viterbi buffer; one or two on the punctured path): see k_rs_overrun
                     const bool by_call = punc.rate != 0 && (int)punc_win_call.size() >= n_eff;
                     auto call_of = [&](int f) {
@@ -1068,8 +1082,17 @@ namespace sdhip
                         const int64_t w = blk - abs_bits / F; // window of this batch the frame's last bit lies in
                         return (w >= 0 && w < (int64_t)punc_win_call.size()) ? punc_win_call[(size_t)w] : -1 - blk;
                     };
-                    for (int f = 0; f + 1 < nf; f++)
-                        W.frames[f].pad = call_of(f) == call_of(f + 1) ? 1 : 0;
+                    // the call's frames lie back to back from slot 0 of the reference's frame buffer: behind a call's last frame stands what an earlier call
+                    // left in the next slot (a sync marker, if any call so far returned that many frames) or the buffer's initial zeros (k_extract)
+                    for (int f = 0, slot = 0; f < nf; f++)
+                    {
+                        const bool same = f + 1 < nf && call_of(f) == call_of(f + 1);
+                        const int used = slot + 1; // slots this call has filled up to this frame
+                        W.frames[f].pad = same ? FRAME_NEXT_SAME_CALL : (used < rs_slots_used ? FRAME_NEXT_SLOT_USED : 0);
+                        if (!same)
+                            rs_slots_used = std::max(rs_slots_used, used);
+                        slot = same ? slot + 1 : 0;
+                    }
                 }
                 if (nf > 0)
                 {
@@ -1093,6 +1116,7 @@ namespace sdhip
                     fc.rs_fill_bytes = cfg.rs_fill_bytes;
                     fc.rs_dualbasis = cfg.rs_dualbasis;
                     fc.rs_nroots = cfg.rs_type == SDHIP_RS239 ? 16 : 32;
+                    fc.rs_tail = rs_tail;
                     d_rs_clean.reserve(rs_scratch_bytes((long long)nf * I)); // clean flags, syndromes, dirty list (k_rs_screen -> k_rs)
                     launch_frames(bs, fc, d_frames.p, nf, d_fbytes.p, d_ferr.p, stream, d_rs_clean.p);
                     h_dst.assign(nf, -1);
@@ -2979,9 +3003,16 @@ extern "C"
     {
         SD_GUARD_BEGIN
         SD_HIP(hipSetDevice(device));
+        const int nroots = rs_type == SDHIP_RS239 ? 16 : 32;
+        if (nframes < 0 || I < 1 || I > 8 || fill_bytes < -1 || fill_bytes >= 255 - nroots || frame_stride < 4 + (255 - std::max(fill_bytes, 0)) * I)
+            throw HipError("sdhip_op_rs_decode: I or fill_bytes out of range, or a frame stride shorter than the interleaved codeblock and the 4 bytes in front of it");
         DevBuf<uint8_t> clean;
         clean.reserve(rs_scratch_bytes((long long)nframes * I));
-        launch_rs_only(d_data, nframes, frame_stride, dualbasis, I, rs_type == SDHIP_RS239 ? 16 : 32, fill_bytes, d_errors, nullptr, clean.p);
+        launch_rs_only(d_data, nframes, frame_stride, dualbasis, I, nroots, fill_bytes, d_errors, nullptr, clean.p);
+        // rs_fill_bytes = -1 and a frame longer than its codeblock (d_data points 4 bytes into a frame of frame_stride bytes, as in the modules):
+        // the byte the reference's 256-byte interleave leaves in the frame's own tail (k_rs_overrun). The op knows no successors.
+        if (fill_bytes == -1 && 4 + 255 * I < frame_stride)
+            launch_rs_overrun(d_data - 4, nullptr, nframes, frame_stride, I, dualbasis, d_errors, nullptr);
         SD_HIP(hipDeviceSynchronize());
         return 0;
         SD_GUARD_END(-1)

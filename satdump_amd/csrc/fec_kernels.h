@@ -211,14 +211,19 @@ namespace sdhip
         uint32_t asm_sync;
         int derand, derand_after_rs, derand_start;
         int rs_i, rs_fill_bytes, rs_dualbasis, rs_nroots; // rs_nroots 32 (rs223) / 16 (rs239); rs_i == 0 disables RS
+        int rs_tail = 0; // bytes by which the interleaved codeblock (4 + (255 - max(fill, 0)) * rs_i) is longer than the CADU, 0..4: RS reads them behind the frame
     };
+    // FrameDesc::pad, what lies behind the frame in the reference's frame buffer (module_ccsds_conv_concat_decoder.cpp:171-175: the frames of ONE
+    // deframer call lie back to back from slot 0): its successor, or what an earlier call left in the next slot, or (neither bit) zeros
+    constexpr int FRAME_NEXT_SAME_CALL = 1; // the next frame of the batch came from the same deframer call
+    constexpr int FRAME_NEXT_SLOT_USED = 2; // no such successor, but an earlier call filled the next slot: a sync marker stands there
     struct FrameDesc
     {
         int64_t pos; // logical bit position of the first payload bit (the bit after the ASM)
         int inv;     // bit_inversion
-        int pad;
+        int pad;     // FRAME_NEXT_*
     };
-    // frames: nframes descriptors; out: nframes * cadu_bytes; errors: nframes * max(rs_i,1) ints (-1 = uncorrectable)
+    // frames: nframes descriptors; out: nframes * cadu_bytes + rs_tail; errors: nframes * max(rs_i,1) ints (-1 = uncorrectable)
     // clean_scratch (optional, rs_scratch_bytes(nframes * rs_i) bytes): enables the syndrome screen in front of the thread-per-codeword
     // decoder (a clean flag per codeword, then the 32 syndromes of every codeword, which the decoder takes over instead of evaluating
     // them again, then the count and the ids of the codewords with a non-zero syndrome: the decoder runs over that compacted list)
@@ -229,6 +234,9 @@ namespace sdhip
     // Unit entry: RS decode of frames already in memory (sdhip_op_rs_decode).
     void launch_rs_only(uint8_t *data, int nframes, int frame_stride, int dualbasis, int I, int nroots, int fill_bytes, int *errors, hipStream_t st,
                         uint8_t *clean_scratch = nullptr);
+    // rs_fill_bytes = -1: the byte the reference's 256-byte interleave leaves at offset 4 + 255 I + b of a frame (k_rs_overrun); out: the frames from their
+    // first byte (4 in front of the codeblock), frames: may be null (no successors), errors: what launch_rs_only left
+    void launch_rs_overrun(uint8_t *out, const FrameDesc *frames, int nframes, int stride, int I, int dualbasis, const int *errors, hipStream_t st);
     // Compaction: copy frames whose keep[i] != 0 to out in order. Returns nothing; count known to the host.
     void launch_compact(const uint8_t *frames, const int *dst_index, int nframes, int cadu_bytes, uint8_t *out, hipStream_t st);
     // rs_usecheck filter + output slots on the device (fec_kernels.hip: k_rs_filter): dst[f] = out_base + (kept frames in front of f) or -1; info[0] = kept, info[1 + k] = last frame's errors[k]

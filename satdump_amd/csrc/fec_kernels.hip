@@ -2654,7 +2654,7 @@ namespace sdhip
         const int f = (int)(cwid / I), b = (int)(cwid % I);
         unsigned char *base = data + (size_t)f * frame_stride;
         unsigned char *cw = cwbuf + tid;
-        const int fb = fill_bytes < 0 ? 0 : fill_bytes; // fill_bytes == -1: no depuncture (the 256th-byte overrun is not reproduced)
+        const int fb = fill_bytes < 0 ? 0 : fill_bytes; // fill_bytes == -1: no depuncture (the 256th byte's overrun: k_rs_overrun)
         const int coded = 255 - nroots;
         // deinterleave + depuncture (reedsolomon.cpp:65-69,145-149) + dual->conventional
         for (int k = 0; k < 255; k++)
@@ -2919,7 +2919,13 @@ namespace sdhip
         {
             unsigned v;
             if (w == 0)
+            {
                 v = fc.asm_sync; // reset_frame writes the constant ASM, bpsk_ccsds_deframer.cpp:115-123
+                // a frame rs_tail bytes shorter than its codeblock: RS of frame f - 1 reads these bytes. Where the reference's frame buffer holds zeros
+                // behind that frame (FRAME_NEXT_* both clear), so do they until k_rs_markers puts the marker back
+                if (fc.rs_tail > 0 && f > 0 && (frames[f - 1].pad & (FRAME_NEXT_SAME_CALL | FRAME_NEXT_SLOT_USED)) == 0)
+                    v = fc.rs_tail >= 4 ? 0u : (v & (0xFFFFFFFFu >> (8 * fc.rs_tail)));
+            }
             else
             {
                 v = stream32(bs, d.pos + (long long)(w - 1) * 32);
@@ -2937,6 +2943,9 @@ namespace sdhip
                 o[k] = (unsigned char)byte;
             }
         }
+        // ... and behind the batch's last frame: the marker of the frame that lay in the reference's next slot before, or that slot's zeros
+        if (f == nframes - 1 && (int)threadIdx.x < fc.rs_tail)
+            o[fc.cadu_bytes + (int)threadIdx.x] = (d.pad & FRAME_NEXT_SLOT_USED) ? (unsigned char)(fc.asm_sync >> (24 - 8 * (int)threadIdx.x)) : (unsigned char)0;
     }
     __global__ __launch_bounds__(256) void k_derand(unsigned char *frames, int nframes, int cadu_bytes, int derand_start, const GfTables *tabs)
     {
@@ -2955,15 +2964,43 @@ namespace sdhip
     // frames from one call (CADUs shorter than half a Viterbi buffer: the 2048 / 2072-bit pipelines) that next frame is real:
     // its first rs_i bytes -- sync marker bytes, rs_i <= 4 -- come out as those values. FrameDesc::pad marks a frame whose
     // successor came from the same call.
+    // In general: after a successful decode of codeword b, that byte lies at offset T = 4 + 255 I + b from the frame's start, in the
+    // reference's buffer. T < cadu_bytes (a frame longer than its codeblock): inside the frame itself, successor or not. Otherwise at byte
+    // T - cadu_bytes of the next frame, if that one came from the same call (below 4, the sync marker: the engine refuses configurations
+    // that would reach the successor's data). A thread per codeword (I up to 8); frames == nullptr (sdhip_op_rs_decode): no successors.
     __global__ __launch_bounds__(256) void k_rs_overrun(unsigned char *out, const FrameDesc *frames, int nframes, int cadu_bytes, int I, int dualbasis,
                                                          const int *errors, const GfTables *tabs)
     {
         const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-        const int f = idx >> 2, b = idx & 3;
-        if (f + 1 >= nframes || b >= I || !frames[f].pad || errors[(size_t)f * I + b] < 0)
+        const int f = idx / I, b = idx - f * I;
+        if (f >= nframes || errors[(size_t)f * I + b] < 0)
             return;
+        const int flags = frames ? frames[f].pad : 0;
+        const int T = 4 + 255 * I + b;
         const unsigned v = out[(size_t)f * cadu_bytes + 4 + b];
-        out[(size_t)(f + 1) * cadu_bytes + b] = dualbasis ? tabs->from_dual[v] : (unsigned char)v;
+        const unsigned char w = dualbasis ? tabs->from_dual[v] : (unsigned char)v;
+        if (T < cadu_bytes)
+            out[(size_t)f * cadu_bytes + T] = w;
+        else if ((flags & FRAME_NEXT_SAME_CALL) && f + 1 < nframes && T - cadu_bytes < 4)
+            out[(size_t)(f + 1) * cadu_bytes + (T - cadu_bytes)] = w;
+    }
+    void launch_rs_overrun(uint8_t *out, const FrameDesc *frames, int nframes, int stride, int I, int dualbasis, const int *errors, hipStream_t st)
+    {
+        if (nframes <= 0 || I <= 0)
+            return;
+        ProfScope _ps("k_rs_overrun", st);
+        hipLaunchKernelGGL(k_rs_overrun, dim3((unsigned)((nframes * I + 255) / 256)), dim3(256), 0, st, out, frames, nframes, stride, I, dualbasis, errors,
+                           tables_for_current_device());
+    }
+    // Frames rs_tail bytes shorter than their codeblock: k_extract left zeros in the first rs_tail bytes of a frame whose predecessor's RS had to
+    // read zeros there (neither FRAME_NEXT_* bit). RS is done: the sync marker goes back. A thread per frame.
+    __global__ __launch_bounds__(256) void k_rs_markers(unsigned char *out, const FrameDesc *frames, int nframes, int cadu_bytes, int rs_tail, unsigned asm_sync)
+    {
+        const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+        if (f + 1 >= nframes || (frames[f].pad & (FRAME_NEXT_SAME_CALL | FRAME_NEXT_SLOT_USED)) != 0)
+            return;
+        for (int j = 0; j < rs_tail && j < 4; j++)
+            out[(size_t)(f + 1) * cadu_bytes + j] = (unsigned char)(asm_sync >> (24 - 8 * j));
     }
 
     void launch_frames(const BitStream &bs, const FrameCfg &fc, const FrameDesc *frames, int nframes, uint8_t *out, int *errors, hipStream_t st, uint8_t *clean_scratch)
@@ -2977,12 +3014,16 @@ namespace sdhip
         }
         if (fc.rs_i != 0)
             launch_rs_only(out + 4, nframes, fc.cadu_bytes, fc.rs_dualbasis, fc.rs_i, fc.rs_nroots, fc.rs_fill_bytes, errors, st, clean_scratch);
-        if (fc.rs_i != 0 && fc.rs_fill_bytes == -1 && nframes > 1)
+        const bool restore_markers = fc.rs_i != 0 && fc.rs_tail > 0 && nframes > 1;
+        if (restore_markers)
         {
-            ProfScope _ps("k_rs_overrun", st);
-            hipLaunchKernelGGL(k_rs_overrun, dim3((unsigned)((nframes * 4 + 255) / 256)), dim3(256), 0, st, out, frames, nframes, fc.cadu_bytes, fc.rs_i, fc.rs_dualbasis,
-                               errors, tabs);
+            ProfScope _ps("k_rs_markers", st);
+            hipLaunchKernelGGL(k_rs_markers, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, st, out, frames, nframes, fc.cadu_bytes, fc.rs_tail, (unsigned)fc.asm_sync);
         }
+        const bool overrun = fc.rs_i != 0 && fc.rs_fill_bytes == -1;
+        const bool own_tail_target = 4 + 255 * fc.rs_i < fc.cadu_bytes; // a frame longer than its codeblock; else only a successor can be written
+        if (overrun && (own_tail_target || nframes > 1))
+            launch_rs_overrun(out, frames, nframes, fc.cadu_bytes, fc.rs_i, fc.rs_dualbasis, errors, st);
         if (fc.derand && fc.derand_after_rs)
         {
             const long long n = (long long)nframes * fc.cadu_bytes;

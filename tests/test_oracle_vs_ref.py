@@ -10,6 +10,7 @@ import pytest
 
 from oracle import pyref
 from satdump_amd import synth
+from tests import test_fec_gpu as G  # the frames and streams of its RS matrix (builders only: nothing of it runs here)
 from tests import util
 
 
@@ -87,6 +88,31 @@ def test_rs_decode_with_errors_port_equals_ref(ref, port):
         b, eb = port.rs_decode(frames, fill_bytes=fill)
         assert np.array_equal(ea, eb) and np.array_equal(a, b)
     assert (ea == -1).any() and (ea > 0).any()
+    # ... and over the matrix the GPU tests run (tests/test_fec_gpu.py: both codes, I = 1..8, both bases, shortened codes, frames longer than
+    # their codeblock), so that the restatement stands in for the reference wherever oracle/_ref is not at hand
+    cases = [(rs, I, dual, fill, 0) for rs in ("rs223", "rs239") for I in (1, 2, 3, 4, 5, 8) for dual in (0, 1) for fill in (-1, 0, 3, 7, 16)]
+    cases += [(rs, I, 1, -1, 6) for rs in ("rs223", "rs239") for I in (1, 4, 5, 8)]
+    for rs, I, dual, fill, extra in cases:
+        frames = G._rs_unit_frames(rs, I, dual, fill, extra=extra)
+        a, ea = ref.rs_decode(frames, I=I, dualbasis=bool(dual), rs239=rs == "rs239", fill_bytes=fill)
+        b, eb = port.rs_decode(frames, I=I, dualbasis=bool(dual), rs239=rs == "rs239", fill_bytes=fill)
+        assert np.array_equal(ea, eb) and np.array_equal(a, b), (rs, I, dual, fill, extra)
+        assert (ea == -1).any() and (ea > 0).any() and (ea == 0).any() and not np.array_equal(a, frames)
+
+
+@pytest.mark.parametrize("usecheck", [0, 1])
+@pytest.mark.parametrize("name", list(G._TAIL_CASES))
+def test_rs_tail_of_the_shipped_pipelines_port_equals_ref(ref, port, name, usecheck):
+    """concat_decode / simple_decode of the restatement == the compiled reference on the module rows of tests/test_fec_gpu.py
+    (RS(255,239), I = 1, 5, 8, shortened codes, bpsk_90, frames shorter and longer than their codeblock)."""
+    soft, plain = G._tail_case(name)
+    oc = G._tail_ocfg(name, usecheck)
+    simple = G._TAIL_CASES[name][0] == "simple"
+    a = ref.simple_decode(oc, soft) if simple else ref.concat_decode(oc, soft)
+    b = port.simple_decode(oc, soft) if simple else port.concat_decode(oc, soft)
+    for k in ("cadu", "frm_err", "n_deframed") + (() if simple else ("ber", "state")):
+        assert np.array_equal(a[k], b[k]), k
+    G._assert_tail_input(name, a, plain, usecheck)
 
 
 def test_deframer_port_equals_ref(ref, port):
