@@ -1218,8 +1218,9 @@ namespace sdhip
     // (inverted) decisions along the path that SURVIVES in s. That byte is all a traceback needs: 8 decoded bits at a time, and the state 8 steps
     // earlier is the bit reversal of the first six of them (each step back shifts the state right and enters the decision at bit 5, cc_decoder.cpp:
     // 250-260). Per step this drops the two v_and_or (tag back on), the v_perm and the v_lshl_or (decision words) of every butterfly pair -- 13 -> 9
-    // instructions, + 16 v_or per step for the tagged constants, + 48 per group to gather and clear the bytes -- and the traceback makes one dependent
-    // byte fetch per 8 steps. Storage is what it was: 64 bytes per 8 steps and lane, as four uint4 planes [group][v][unit].
+    // instructions, + 48 per group to gather and clear the bytes; the tag costs one packed subtraction per step (it enters the eight branch constants
+    // through the renormalisation term they all subtract, and four of the eight are the other four with their halves exchanged: v2h_acs) -- and the
+    // traceback makes one dependent byte fetch per 8 steps. Storage is what it was: 64 bytes per 8 steps and lane, as four uint4 planes [group][v][unit].
     __device__ __forceinline__ void v2h_init_neutral(V2State &s)
     {
 #pragma unroll
@@ -1243,29 +1244,33 @@ namespace sdhip
         s.C2 = 0u;
     }
     // one trellis step, the KSTEP-th of its group; DEC = false: no tags (the low bytes stay as they are -- clear, in a warm-up)
+    // PD[k] = D[k] | D[3 - k] << 16, k = 0, 1: the four branch metrics of the step, ((sum + 1) >> 3) << 8 each, paired as the butterflies take them
+    // (D[k] belongs to the symbol pair (s0 or its complement: k >> 1, s1 or its complement: k & 1); PD[3 - k] is PD[k] with its halves exchanged)
     template <int KSTEP, bool DEC>
-    __device__ __forceinline__ void v2h_step(V2State &s, unsigned sym)
+    __device__ __forceinline__ void v2h_acs(V2State &s, const unsigned (&PD)[2])
     {
-        const unsigned s0 = sym & 255u, s1 = (sym >> 8) & 255u;
-        const unsigned a[2] = {s0, s0 ^ 255u}, c[2] = {s1, s1 ^ 255u};
-        unsigned D[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            D[k] = ((a[k >> 1] + c[k & 1] + 1u) << 5) & 0x3F00u; // ((sum + 1) >> 3) << 8
-        const unsigned Q = pk_sub(0x3F003F00u, s.C2);
-        constexpr unsigned TL = DEC ? (1u << KSTEP) : 0u, TH = TL << 16;
+        constexpr unsigned TL = DEC ? (1u << KSTEP) : 0u;
         // candidates (see the register map above): T1 = (m0, m3'), T2 = (m1, m2'), T3 = (m2, m1'), T4 = (m3, m0'); a tie goes to m1 / m3 / m3' / m1'
-        // (decision = (m0 - m1) >= 0 picks the second), so m0, m2 (low halves of T1, T3) and m2', m0' (high halves of T2, T4) carry the tag
-        unsigned K1a[4], K1b[4], K2a[4], K2b[4];
+        // (decision = (m0 - m1) >= 0 picks the second), so m0, m2 (low halves of T1, T3) and m2', m0' (high halves of T2, T4) carry the tag.
+        // The constants are K1 = PD - C2 and K2 = Q - PD (Q = 0x3F003F00 - C2), tagged low (K1a = K1 | TL, K2b = K2 | TL) or high (K1 | TL << 16,
+        // K2 | TL << 16). C2 and Q have equal halves and PD[3 - k] is PD[k] exchanged, so the high-tagged constants are the low-tagged ones of 3 - k
+        // exchanged -- an op_sel of the packed add, no instruction. And the low tag rides in on the one operand all eight share: all low bytes of PD,
+        // C2 and Q are zero, so with Ct = C2 - TL (low half only; 16-bit arithmetic per half) K1a = PD - Ct and K2b = (0x3F003F00 - Ct) - PD.
+        unsigned Ct = pk_sub(s.C2, TL);
+#ifndef SDHIP_HOST_TWIN
+        asm("" : "+v"(Ct)); // (the two keep PD - Ct and Qt - PD one subtraction each: the compiler rewrites them to (PD - C2) + TL and const - (Ct + PD))
+#endif
+        unsigned Qt = pk_sub(0x3F003F00u, Ct);
+#ifndef SDHIP_HOST_TWIN
+        asm("" : "+v"(Qt));
+#endif
+        unsigned K1a[4], K2b[4];
 #pragma unroll
         for (int k = 0; k < 4; k++)
         {
-            const unsigned PD = D[k] | (D[3 - k] << 16);
-            const unsigned K1 = pk_sub(PD, s.C2), K2 = pk_sub(Q, PD);
-            K1a[k] = K1 | TL;
-            K1b[k] = K1 | TH;
-            K2a[k] = K2 | TH;
-            K2b[k] = K2 | TL;
+            const unsigned P = k < 2 ? PD[k] : pk_swap(PD[3 - k]);
+            K1a[k] = pk_sub(P, Ct);
+            K2b[k] = pk_sub(Qt, P);
         }
         unsigned Rn[32];
         unsigned mnA = 0xFFFFFFFFu, mnB = 0xFFFFFFFFu;
@@ -1275,8 +1280,8 @@ namespace sdhip
             const int b0 = (i ^ (i >> 1) ^ (i >> 2)) & 1, b1 = ((i >> 1) ^ (i >> 2) ^ (i >> 4)) & 1;
             const int k = b0 * 2 + b1;
             const unsigned R1 = s.R[i], R2 = pk_swap(s.R[31 - i]);
-            const unsigned E = pk_min(pk_add(R1, K1a[k]), pk_add(R2, K2a[k]));
-            const unsigned O = pk_min(pk_add(R1, K2b[k]), pk_add(R2, K1b[k]));
+            const unsigned E = pk_min(pk_add(R1, K1a[k]), pk_add(R2, pk_swap(K2b[3 - k])));
+            const unsigned O = pk_min(pk_add(R1, K2b[k]), pk_add(R2, pk_swap(K1a[3 - k])));
             Rn[2 * i] = E;
             Rn[2 * i + 1] = O;
             mnA = pk_min(mnA, E);
@@ -1289,17 +1294,36 @@ namespace sdhip
         const unsigned m1 = min(mn & 0xFFFFu, mn >> 16) & 0xFF00u;
         s.C2 = m1 | (m1 << 16);
     }
+    // two trellis steps (K0, K0 + 1 of the group) from one dword of symbols (s0 | s1 << 8 of step K0 in the low half, of step K0 + 1 in the high half):
+    // the four branch metrics of both steps in the halves of four registers -- symbols shifted first, (s0 + 1) << 5 and s1 << 5 and their complements,
+    // so that a sum is one packed add and one mask; it stays below 2^16 per half (511 << 5 at most): the packed form is exact --, then a step's PD[k]
+    // is one v_perm of two of them.
+    template <int K0, bool DEC>
+    __device__ __forceinline__ void v2h_pair(V2State &s, unsigned x)
+    {
+        const unsigned a = (x << 5) & 0x1FE01FE0u, c = (x >> 3) & 0x1FE01FE0u;    // s0 << 5, s1 << 5
+        const unsigned a1[2] = {pk_add(a, 0x00200020u), pk_sub(0x20002000u, a)}; // (s0 + 1) << 5, ((255 - s0) + 1) << 5
+        const unsigned c0[2] = {c, c ^ 0x1FE01FE0u};                             // s1 << 5, (255 - s1) << 5
+        unsigned D2[4], PD[2];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            D2[k] = pk_add(a1[k >> 1], c0[k & 1]) & 0x3F003F00u; // ((sum + 1) >> 3) << 8, twice
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+            PD[k] = __builtin_amdgcn_perm(D2[3 - k], D2[k], 0x05040100u);
+        v2h_acs<K0, DEC>(s, PD);
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+            PD[k] = __builtin_amdgcn_perm(D2[3 - k], D2[k], 0x07060302u);
+        v2h_acs<K0 + 1, DEC>(s, PD);
+    }
     template <bool DEC>
     __device__ __forceinline__ void v2h_group(V2State &s, const uint4 q)
     {
-        v2h_step<0, DEC>(s, q.x & 0xFFFFu);
-        v2h_step<1, DEC>(s, q.x >> 16);
-        v2h_step<2, DEC>(s, q.y & 0xFFFFu);
-        v2h_step<3, DEC>(s, q.y >> 16);
-        v2h_step<4, DEC>(s, q.z & 0xFFFFu);
-        v2h_step<5, DEC>(s, q.z >> 16);
-        v2h_step<6, DEC>(s, q.w & 0xFFFFu);
-        v2h_step<7, DEC>(s, q.w >> 16);
+        v2h_pair<0, DEC>(s, q.x);
+        v2h_pair<2, DEC>(s, q.y);
+        v2h_pair<4, DEC>(s, q.z);
+        v2h_pair<6, DEC>(s, q.w);
     }
     // the 64 history bytes of a group: dword q = states (2q, 63 - 2q, 2q + 1, 62 - 2q), byte 0 first
     __device__ __forceinline__ void v2h_gather(const V2State &s, unsigned (&rec)[16])
@@ -1424,12 +1448,9 @@ namespace sdhip
         }
         if (g == NSEG - 1)
         {
-            v2h_step<0, true>(s, q.x & 0xFFFFu);
-            v2h_step<1, true>(s, q.x >> 16);
-            v2h_step<2, true>(s, q.y & 0xFFFFu);
-            v2h_step<3, true>(s, q.y >> 16);
-            v2h_step<4, true>(s, q.z & 0xFFFFu);
-            v2h_step<5, true>(s, q.z >> 16);
+            v2h_pair<0, true>(s, q.x);
+            v2h_pair<2, true>(s, q.y);
+            v2h_pair<4, true>(s, q.z);
             v2h_gather(s, rec);
 #pragma unroll
             for (int v = 0; v < 4; v++)
