@@ -11,7 +11,9 @@ import pytest
 
 gpu = pytest.mark.gpu  # every test but test_defaults needs the device
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ldpc")
-STREAMS = ["r78_qpsk_direct", "r78_oqpsk_internal", "r78_bpsk", "r78_noise"]
+STREAMS = ["r78_qpsk_direct", "r78_oqpsk_internal", "r78_bpsk", "r78_noise", "r78_rails"]
+# four frames each: shorter than the byte positions the ragged cut is written for, so they take the one-call, three-call and correlator tests only
+SHORT_RAILS = ["r78_rails_oqpsk", "r78_rails_bpsk"]
 F, CW, DATA = 8192, 8160, 7136
 
 
@@ -121,7 +123,28 @@ def test_unit_decode_bit_exact(torch_cuda, capi, iterations):
 
 
 @gpu
-@pytest.mark.parametrize("name", STREAMS)
+@pytest.mark.parametrize("iterations", [1, 10])
+def test_unit_decode_rails(torch_cuda, capi, iterations):
+    """prepared codewords quantised to the whole int8 range, 7 % of them -128 (what the soft derandomiser makes of a 127): bits and return values of CCSDSLDPC::decode"""
+    g = _golden("r78_rails")
+    cw = g["rails_codewords"]
+    n = len(cw)
+    assert (np.asarray(cw) == -128).mean() >= 0.05
+    right = {it: (np.asarray(g[f"rails_bits_{it}"]) == np.asarray(g["rails_words"])).all(1) for it in (1, 10)}  # by the fixture alone: the words are decodable, not trivially
+    assert right[10].sum() >= 4 and (right[10] & ~right[1]).any()
+    d_cw = _dev(torch_cuda, cw)
+    d_bits = torch_cuda.zeros(n * CW, dtype=torch_cuda.uint8, device="cuda")
+    d_corr = torch_cuda.zeros(n, dtype=torch_cuda.int32, device="cuda")
+    rc = capi.lib().sdhip_op_ccsds_ldpc_decode(0, capi.CCSDS_LDPC_RATES["7/8"], iterations, d_cw.data_ptr(), n, d_bits.data_ptr(), d_corr.data_ptr())
+    assert rc == 0, capi.last_error()
+    bits = d_bits.cpu().numpy().reshape(n, CW)
+    assert bits.max() <= 1
+    assert np.array_equal(np.packbits(bits, axis=1), g[f"rails_bits_{iterations}"])
+    assert np.array_equal(d_corr.cpu().numpy(), g[f"rails_corrections_{iterations}"])
+
+
+@gpu
+@pytest.mark.parametrize("name", STREAMS + SHORT_RAILS)
 def test_unit_correlator_bit_exact(torch_cuda, capi, name):
     """per position of the first four frames: the correlation (float bits) and the syncword index -- which also proves the tables' six phasor literals"""
     g = _golden(name)
@@ -139,14 +162,14 @@ def test_unit_correlator_bit_exact(torch_cuda, capi, name):
 
 
 @gpu
-@pytest.mark.parametrize("name", STREAMS)
+@pytest.mark.parametrize("name", STREAMS + SHORT_RAILS)
 def test_stream_one_call(torch_cuda, capi, name):
     g = _golden(name)
     _check(g, *_run(torch_cuda, capi, g, [0, len(g["soft"])]))
 
 
 @gpu
-@pytest.mark.parametrize("name", STREAMS)
+@pytest.mark.parametrize("name", STREAMS + SHORT_RAILS)
 def test_stream_three_calls(torch_cuda, capi, name):
     g = _golden(name)
     n = len(g["soft"])

@@ -20,6 +20,7 @@ def torch_cuda():
 
 
 test_defaults = G.test_defaults
+test_unit_decode_rails = _plain(G.test_unit_decode_rails)
 test_unit_correlator_bit_exact = _plain(G.test_unit_correlator_bit_exact)
 test_stream_one_call = _plain(G.test_stream_one_call)
 test_noise_stream_terminates = _plain(G.test_noise_stream_terminates)
@@ -34,7 +35,7 @@ def test_unit_decode_bit_exact(torch_cuda, capi, iterations):
     G.test_unit_decode_bit_exact(torch_cuda, capi, iterations)
 
 
-@pytest.mark.parametrize("name", SHORT)
+@pytest.mark.parametrize("name", SHORT + G.SHORT_RAILS)
 def test_stream_three_calls(torch_cuda, capi, name):
     G.test_stream_three_calls(torch_cuda, capi, name)
 

@@ -98,6 +98,37 @@ def test_sse_batches_share_one_early_exit(capi, fs, rate):
         assert not np.array_equal(solo[3:16], got[3:16]), "clean frames of a mixed batch should have been updated along with the noisy ones"
 
 
+def rails_case(capi, fs, rate, sse):
+    """Frames at amplitude 60, sigma 25, clipped to the WHOLE int8 range (make_frames stops at +-127): -128 among the inputs."""
+    from tests import dvbs2_util
+    ref = _ref(sse)
+    rc = capi.S2_RATES[rate]
+    n, k = ref.dims(fs, rc)
+    nframes = 16 if sse else 3
+    rng = np.random.default_rng(60 + fs)
+    bits = dvbs2_util.encode(fs, rc, rng.integers(0, 2, (nframes, k), dtype=np.uint8))
+    soft = np.clip(np.rint(np.where(bits > 0, -1.0, 1.0) * 60 + rng.standard_normal(bits.shape) * 25.0), -128, 127).astype(np.int8)
+    assert ((soft == -128).sum(1) > 0).all() and ((soft == 127).sum(1) > 0).all()
+    want, wt = ref.ldpc_decode(fs, rc, soft, 12)
+    assert (wt >= 0).all() and np.array_equal((want[:, :k] < 0).astype(np.uint8), bits[:, :k])  # by the reference alone: the frames decode, to the data sent
+    dec = capi.LdpcDecoder(framesize=fs, rate=rate, batch=ref.batch)
+    got = soft.copy()
+    gt = dec.decode(got, 12)
+    assert np.array_equal(gt, wt), (gt.tolist(), wt.tolist())
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("sse", [False, True], ids=["generic_batch1", "sse_batch16"])
+@pytest.mark.parametrize("fs,rate", [(0, "2/3"), (1, "1/2")])
+def test_int8_rail_inputs(capi, fs, rate, sse):
+    """-128 at the LDPC decoder's input (tests/test_soft_rails_gpu.py has the other decoders): soft bits and trial counts identical to the reference's, batch = 1
+    against its generic build and batch = 16 against its SSE4.1 build -- each mode is held to the build it mirrors, whatever the two builds make of -128
+    between themselves. The reference's own demapper cannot emit -128: constellation_t::clamp (constellation.cpp:289-298, behind demod_soft_calc's LLRs, which
+    demod_soft_lut's table holds; dvbs2_bb_to_soft.cpp:62) halves a finite value until it lies in [-127, 127] and truncates towards zero, and a non-finite one is
+    converted as it is (not defined by the language; 0 on x86). So -128 reaches BBFrameLDPC only from another producer's soft frames, which the entry accepts."""
+    rails_case(capi, fs, rate, sse)
+
+
 def test_device_entry_and_many_frames(capi):
     """sdhip_ldpc_decode_dev on frames resident in HBM, a few hundred frames (more workgroups than CUs), normal 2/3 (BASELINE configs[4]'s
     MODCOD 13): identical to the reference on all of them, and (size-independent property) the converged frames carry their data."""

@@ -45,6 +45,11 @@ def test_codes_bit_exact_on_the_twin(capi, fs, rate):
     G.run_case(capi, ref, fs, rate, 1, 60, 1.0, 5, seed=2)
 
 
+@pytest.mark.parametrize("sse", [False, True])
+def test_int8_rail_inputs_on_the_twin(capi, sse):
+    G.rails_case(capi, 1, "1/2", sse)
+
+
 def test_sse_batch_on_the_twin(capi):
     ref = G._ref(True)
     rc = capi.S2_RATES["1/2"]

@@ -52,6 +52,9 @@ def _symbols(rng, F, nb, kind):
         u = rng.choice(np.array([126, 127, 129], dtype=np.int64), size=nb * 2 * F)
         u[rng.random(len(u)) < 0.2] = 128
         soft = None
+    elif kind == "full_u8":  # the whole byte range: 255 never arises from soft + 127 (tests/test_soft_rails_gpu.py)
+        u = rng.integers(0, 256, nb * 2 * F)
+        soft = None
     else:
         raise ValueError(kind)
     if soft is not None:

@@ -21,7 +21,13 @@ r78_unit.npz holds 16 prepared codewords at three noise levels and, for 1, 10 an
 code's row list; and `g_*`: a small irregular code (check nodes of 3 .. 9 edges, odd degrees among them), words for it, and LDPCDecoderGeneric's bits and return
 values on that row list after 1 and 6 iterations.
 
-The generator asserts, and fails otherwise: the output is the same for three cuttings of each stream; in r78_qpsk_direct and r78_oqpsk_internal at least half of the
+r78_rails.npz, r78_rails_oqpsk.npz and r78_rails_bpsk.npz are streams quantised to the WHOLE int8 range at an amplitude that saturates (12 QPSK frames in the four
+turns, 4 OQPSK frames of the two Q-shifted tables, 4 BPSK frames with the second half inverted): -128 in front of rotate_soft, and, where the stream is derandomised,
+127s that the soft derandomiser turns into -128 in front of the decoder. r78_rails.npz also holds `rails_*`: 8 prepared codewords with -128 among them and
+CCSDSLDPC::decode's bits and return values on them after 1 and 10 iterations.
+
+The generator asserts, and fails otherwise: in every rails stream at least 2 % of the bytes are -128 and at least 2 % are 127, and at least 8 of r78_rails' 12 frames
+are corrected to the transmitted word; the output is the same for three cuttings of each stream; in r78_qpsk_direct and r78_oqpsk_internal at least half of the
 frames have corrections > 0 and decode to the transmitted word; every noisy case has a frame that does not; in r78_unit a word is right after 10 iterations and
 wrong after 1; every syncword index of each constellation occurs in some descriptor."""
 import argparse
@@ -237,6 +243,50 @@ def make_bpsk(enc, rng):
     return s, words, dict(inverted_from=8)
 
 
+# ---- the int8 rails: streams quantised to the whole int8 range, strong enough to saturate. rotate_soft turns every -128 into -127 (rotation.cpp:9-11) before the
+# turn; derand_ccsds_soft then complements the bytes under a PN one, so that every 127 of such a byte reaches CCSDSLDPC::decode as -128
+AMP_R, SIGMA_R = 90.0, 36.0  # some 7 % of the bytes at each rail, some 50 hard-decision errors in a frame
+
+
+def quantise_rails(v: np.ndarray) -> np.ndarray:
+    return np.clip(np.rint(v), -128, 127).astype(np.int8)
+
+
+def make_rails_qpsk(enc, rng):
+    words = [enc.encode(rng.integers(0, 2, DATA).astype(np.uint8)) for _ in range(12)]
+    turns = [0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3]
+    iq = []
+    for w, t in zip(words, turns):
+        p = pairs_stream(wire_frame(w, True))
+        for _ in range(t):
+            p = np.stack([-p[:, 1], p[:, 0]], axis=1)
+        iq.append(p)
+    v = np.concatenate(iq).reshape(-1) * AMP_R
+    return quantise_rails(v + SIGMA_R * rng.standard_normal(len(v))), words, dict(turns=turns, amp=AMP_R, sigma=SIGMA_R)
+
+
+def make_rails_oqpsk(enc, rng):
+    words = [enc.encode(rng.integers(0, 2, DATA).astype(np.uint8)) for _ in range(4)]
+    kinds = [2, 2, 3, 3]  # the tables whose Q rail the module shifts back
+    out = []
+    for w, k in zip(words, kinds):
+        p = pairs_stream(wire_frame(w, True))
+        if k == 3:
+            p = -p
+        p = p.copy()
+        p[:, 1] = np.concatenate([[0.0], p[:-1, 1]])
+        out.append(p)
+    v = np.concatenate(out).reshape(-1) * AMP_R
+    return quantise_rails(v + SIGMA_R * rng.standard_normal(len(v))), words, dict(kinds=kinds, amp=AMP_R, sigma=SIGMA_R)
+
+
+def make_rails_bpsk(enc, rng):
+    words = [enc.encode(rng.integers(0, 2, DATA).astype(np.uint8)) for _ in range(4)]
+    v = np.concatenate([wire_frame(w, False).astype(np.float64) * 2.0 - 1.0 for w in words])
+    v[2 * F:] *= -1.0
+    return quantise_rails(v * AMP_R + SIGMA_R * rng.standard_normal(len(v))), words, dict(inverted_from=2, amp=AMP_R, sigma=SIGMA_R)
+
+
 def words_decoded(frames: np.ndarray, words) -> list:
     sent = {packed_frame(w): i for i, w in enumerate(words)}
     return [sent.get(f[4:].tobytes(), -1) for f in frames.reshape(-1, 1024)]
@@ -292,6 +342,31 @@ def main():
         cases.append(("r78_bpsk", dict(constellation=BPSK, derandomize=0, iterations=3, internal_stream=0), s, words, how))
         rng = np.random.default_rng(7804)
         cases.append(("r78_noise", dict(constellation=QPSK, derandomize=1, iterations=10, internal_stream=0), rng.integers(-127, 128, 12 * F).astype(np.int8), [], dict(noise=True)))
+        rng = np.random.default_rng(7806)
+        s, words, how = make_rails_qpsk(enc, rng)
+        cases.append(("r78_rails", dict(constellation=QPSK, derandomize=1, iterations=10, internal_stream=0), s, words, how))
+        rng = np.random.default_rng(7807)
+        s, words, how = make_rails_oqpsk(enc, rng)
+        cases.append(("r78_rails_oqpsk", dict(constellation=OQPSK, derandomize=1, iterations=10, internal_stream=0), s, words, how))
+        rng = np.random.default_rng(7808)
+        s, words, how = make_rails_bpsk(enc, rng)
+        cases.append(("r78_rails_bpsk", dict(constellation=BPSK, derandomize=0, iterations=10, internal_stream=0), s, words, how))
+        # r78_rails' unit part: prepared codewords as CCSDSLDPC::decode may receive them, -128 among them
+        rng = np.random.default_rng(7809)
+        rw = [enc.encode(rng.integers(0, 2, DATA).astype(np.uint8)) for _ in range(8)]
+        rcw = np.stack([quantise_rails((np.concatenate([w[LEAD:], [0, 0]]).astype(np.float64) * 2.0 - 1.0) * AMP_R + SIGMA_R * rng.standard_normal(CW)) for w in rw])
+        assert (rcw == -128).mean() >= 0.05, (rcw == -128).mean()
+        rails_unit = dict(rails_codewords=rcw, rails_words=np.packbits(np.stack([w[LEAD:] for w in rw]), axis=1))
+        rright = {}
+        for it in (1, 10):
+            bits = np.zeros((8, CW), np.uint8)
+            corr = np.zeros(8, np.int32)
+            L.ldpcref_unit(rcw.ctypes.data, 8, it, bits.ctypes.data, corr.ctypes.data)
+            assert bits.max() <= 1
+            rails_unit[f"rails_bits_{it}"] = np.packbits(bits, axis=1)
+            rails_unit[f"rails_corrections_{it}"] = corr
+            rright[it] = np.array([np.array_equal(bits[k, :CW - 2], rw[k][LEAD:]) for k in range(8)])
+        assert rright[10].sum() >= 4 and (rright[10] & ~rright[1]).any(), (rright[1], rright[10])
         for name, p, soft, words, how in cases:
             n = len(soft)
             whole = run_module(L, p, soft, extras=True)
@@ -320,6 +395,13 @@ def main():
                     assert good >= 16, (name, good)
                     assert bad >= 1, (name, bad)
                 assert [i for i in ids if i >= 0] == sorted(set(i for i in ids if i >= 0))
+                if name.startswith("r78_rails"):
+                    lo, hi = float((soft == -128).mean()), float((soft == 127).mean())
+                    line += f", {lo:.3f} of the bytes at -128 and {hi:.3f} at 127"
+                    assert lo >= 0.02 and hi >= 0.02, (name, lo, hi)
+                    assert good >= (8 if name == "r78_rails" else 2), (name, good)
+            if name == "r78_rails":
+                arrays.update(rails_unit)
             if name == "r78_noise":
                 assert (whole["locked"] == 0).all() and len(whole["offset"]) >= 5, "the noise stream must slide at every read"
             if p["internal_stream"]:
