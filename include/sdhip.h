@@ -397,6 +397,18 @@ extern "C"
        allocates once. Off by default; sdhip_pool_enable(0) and sdhip_pool_trim() release what is parked. Process-wide. */
     void sdhip_pool_enable(int on);
     void sdhip_pool_trim(void);
+    /* What the allocator behind every handle has done since the process started, and what is parked now. A block counts as recycled when it came out of the
+       pool, as fresh when it came from the driver. SDHIP_ALLOC_FILL=<0..255> in the environment (read on every hand-out; a test switch, unset by default)
+       fills every block, fresh or recycled, device or pinned, with that byte before its owner sees it: `filled` counts those blocks. */
+    typedef struct sdhip_pool_stats
+    {
+        uint64_t dev_fresh, dev_recycled;            /* device blocks handed out: from hipMalloc / from the pool */
+        uint64_t pin_fresh, pin_recycled;            /* pinned host blocks handed out: from hipHostMalloc / from the pool */
+        uint64_t dev_parked, pin_parked;             /* blocks in the pool now */
+        uint64_t dev_parked_bytes, pin_parked_bytes; /* and their bytes */
+        uint64_t filled;                             /* blocks filled on hand-out (SDHIP_ALLOC_FILL) */
+    } sdhip_pool_stats;
+    int sdhip_pool_get_stats(sdhip_pool_stats *out); /* 0, or -1 for a null pointer */
 
     /* ---- DVB-S2 LDPC soft decoder (BASELINE configs[4]) ---------------------------------------------------
        Replaces dvbs2::BBFrameLDPC (plugins/dvb_support/codings/dvb-s2/bbframe_ldpc.{h,cpp}; decoder = ldpc/layered_decoder.hh with

@@ -143,6 +143,12 @@ class NdspPskCfg(C.Structure):
                 ("exact", C.c_int), ("chunk_len", C.c_int), ("warmup", C.c_int)]
 
 
+class PoolStats(C.Structure):
+    _fields_ = [("dev_fresh", C.c_uint64), ("dev_recycled", C.c_uint64), ("pin_fresh", C.c_uint64), ("pin_recycled", C.c_uint64),
+                ("dev_parked", C.c_uint64), ("pin_parked", C.c_uint64), ("dev_parked_bytes", C.c_uint64), ("pin_parked_bytes", C.c_uint64),
+                ("filled", C.c_uint64)]
+
+
 class SdhipError(RuntimeError):
     pass
 
@@ -309,6 +315,9 @@ def lib():
             L.sdhip_op_generic_correlate.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.sdhip_prof_enable.argtypes = [C.c_int]
         L.sdhip_pool_enable.argtypes = [C.c_int]
+        L.sdhip_pool_trim.argtypes = []
+        L.sdhip_pool_trim.restype = None
+        L.sdhip_pool_get_stats.argtypes = [C.POINTER(PoolStats)]
         L.sdhip_prof_get.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
         _lib = L
     return _lib
@@ -317,6 +326,18 @@ def lib():
 def pool_enable(on: bool = True):
     """Park the device / pinned blocks of destroyed handles for the next handles (sdhip_pool_enable)."""
     lib().sdhip_pool_enable(int(on))
+
+
+def pool_trim():
+    """Release what is parked (sdhip_pool_trim); the pool stays as it is, on or off."""
+    lib().sdhip_pool_trim()
+
+
+def pool_stats() -> PoolStats:
+    """Blocks handed out fresh / recycled and filled since the process started, blocks and bytes parked now (sdhip_pool_get_stats)."""
+    st = PoolStats()
+    _check(lib().sdhip_pool_get_stats(C.byref(st)), "sdhip_pool_get_stats")
+    return st
 
 
 def prof_enable(on: bool = True):

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -43,24 +44,55 @@ namespace sdhip
     static std::multimap<std::pair<int, size_t>, void *> g_pool_dev; // (device, bytes) -> parked block
     static std::multimap<size_t, void *> g_pool_pin;
     static std::map<void *, int> g_dev_of; // device a live block was allocated on
+    static sdhip_pool_stats g_pool_stats = {}; // the counters of sdhip_pool_get_stats (the parked figures are taken from the maps)
+    // SDHIP_ALLOC_FILL=<0..255>, read on every hand-out: the byte every block is filled with before its owner sees it, fresh or recycled (a test switch: what
+    // a handle reads before it writes shows as 0xFF.. / 0x7F.. instead of the zeros of a fresh page or the previous owner's results). -1: unset.
+    static int alloc_fill()
+    {
+        const char *e = getenv("SDHIP_ALLOC_FILL");
+        if (!e || !*e)
+            return -1;
+        char *end = nullptr;
+        const long v = strtol(e, &end, 0);
+        if (*end || v < 0 || v > 255)
+            throw HipError(std::string("SDHIP_ALLOC_FILL must be a byte value 0..255, got \"") + e + "\"");
+        return (int)v;
+    }
+    static void count_handout(bool pinned, bool recycled, bool filled)
+    {
+        std::lock_guard<std::mutex> lk(g_pool_mu);
+        (pinned ? (recycled ? g_pool_stats.pin_recycled : g_pool_stats.pin_fresh) : (recycled ? g_pool_stats.dev_recycled : g_pool_stats.dev_fresh)) += 1;
+        g_pool_stats.filled += filled ? 1 : 0;
+    }
     void *dev_alloc(size_t bytes)
     {
+        const int fill = alloc_fill();
         int dev = 0;
         SD_HIP(hipGetDevice(&dev));
+        void *p = nullptr;
         {
             std::lock_guard<std::mutex> lk(g_pool_mu);
             auto it = g_pool_dev.find({dev, bytes});
             if (it != g_pool_dev.end())
             {
-                void *p = it->second;
+                p = it->second;
                 g_pool_dev.erase(it);
-                return p;
             }
         }
-        void *p = nullptr;
-        SD_HIP(hipMalloc(&p, bytes));
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        g_dev_of[p] = dev;
+        const bool recycled = p != nullptr;
+        if (!recycled)
+        {
+            SD_HIP(hipMalloc(&p, bytes));
+            std::lock_guard<std::mutex> lk(g_pool_mu);
+            g_dev_of[p] = dev;
+        }
+        if (fill >= 0 && bytes)
+        {
+            // on the null stream and waited for here: the handles' streams are non-blocking and would not wait for it
+            SD_HIP(hipMemset(p, fill, bytes));
+            SD_HIP(hipStreamSynchronize(nullptr));
+        }
+        count_handout(false, recycled, fill >= 0);
         return p;
     }
     void dev_free(void *p, size_t bytes)
@@ -100,18 +132,23 @@ namespace sdhip
     }
     void *pin_alloc(size_t bytes)
     {
+        const int fill = alloc_fill();
+        void *p = nullptr;
         {
             std::lock_guard<std::mutex> lk(g_pool_mu);
             auto it = g_pool_pin.find(bytes);
             if (it != g_pool_pin.end())
             {
-                void *p = it->second;
+                p = it->second;
                 g_pool_pin.erase(it);
-                return p;
             }
         }
-        void *p = nullptr;
-        SD_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+        const bool recycled = p != nullptr;
+        if (!recycled)
+            SD_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+        if (fill >= 0)
+            memset(p, fill, bytes);
+        count_handout(true, recycled, fill >= 0);
         return p;
     }
     void pin_free(void *p, size_t bytes)
@@ -2829,6 +2866,21 @@ extern "C"
             sdhip::pool_trim();
     }
     void sdhip_pool_trim(void) { sdhip::pool_trim(); }
+    int sdhip_pool_get_stats(sdhip_pool_stats *out)
+    {
+        if (!out)
+            return -1;
+        std::lock_guard<std::mutex> lk(sdhip::g_pool_mu);
+        *out = sdhip::g_pool_stats;
+        out->dev_parked = sdhip::g_pool_dev.size();
+        out->pin_parked = sdhip::g_pool_pin.size();
+        out->dev_parked_bytes = out->pin_parked_bytes = 0;
+        for (auto &kv : sdhip::g_pool_dev)
+            out->dev_parked_bytes += kv.first.second;
+        for (auto &kv : sdhip::g_pool_pin)
+            out->pin_parked_bytes += kv.first;
+        return 0;
+    }
 
     void sdhip_prof_enable(int on)
     {

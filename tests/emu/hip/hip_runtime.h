@@ -67,11 +67,19 @@ enum
 };
 
 inline const char *hipGetErrorString(hipError_t) { return "host twin"; }
+// Device and pinned memory are uninitialised: both come back poisoned, so that code relying on zeros shows up. EMU_FILL=<0..255> (read at every allocation)
+// chooses the byte; the default is 0xA5. As a float 0xA5A5A5A5 is -2.9e-16 and as a double about -1e-127 -- as good as the zero an accumulator assumes -- so
+// a run that looks for such state sets 255 (NaN, -1) or 127 (3.4e38, +127). (The library's own SDHIP_ALLOC_FILL then refills the blocks of its DevBuf / PinBuf.)
+inline int emu_fill_byte()
+{
+    const char *e = getenv("EMU_FILL");
+    return e && *e ? (int)(strtol(e, nullptr, 0) & 0xFF) : 0xA5;
+}
 inline hipError_t hipMalloc(void **p, size_t n)
-{ // device memory is uninitialised: poison it so that a kernel relying on zeros shows up
+{
     *p = malloc(n ? n : 1);
     if (*p)
-        memset(*p, getenv("EMU_POISON_ZERO") ? 0 : 0xA5, n);
+        memset(*p, emu_fill_byte(), n);
     return *p ? 0 : 2;
 }
 inline hipError_t hipFree(void *p)
@@ -82,6 +90,8 @@ inline hipError_t hipFree(void *p)
 inline hipError_t hipHostMalloc(void **p, size_t n, unsigned)
 {
     *p = malloc(n ? n : 1);
+    if (*p)
+        memset(*p, emu_fill_byte(), n);
     return *p ? 0 : 2;
 }
 inline hipError_t hipHostFree(void *p)

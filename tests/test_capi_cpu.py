@@ -31,6 +31,7 @@ def test_version_and_defaults():
 def test_struct_mirrors_match_the_header():
     """The ctypes mirrors (satdump_amd/capi.py and oracle/pyref.py) against include/sdhip.h: same field names in the same order
     (the structs are plain ints / floats / doubles, so order + count pins the layout)."""
+    import ctypes as C
     import re
     from satdump_amd import capi
     from oracle import pyref
@@ -53,6 +54,8 @@ def test_struct_mirrors_match_the_header():
     assert [f for f, _ in capi.LrptCfg._fields_] == fields("sdhip_lrpt_cfg")
     assert [f for f, _ in capi.LrptStats._fields_] == fields("sdhip_lrpt_stats")
     assert [f for f, _ in capi.Dvbs2Stats._fields_] == fields("sdhip_dvbs2_stats")
+    assert [f for f, _ in capi.PoolStats._fields_] == fields("sdhip_pool_stats")
+    assert all(t is C.c_uint64 for _, t in capi.PoolStats._fields_)  # the header's are all uint64_t
 
 
 def test_product_filter_design_against_the_reference_tables():
