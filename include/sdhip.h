@@ -755,6 +755,72 @@ extern "C"
        at p that is > 0 (else 0) and the first syncword reaching it. d_cor / d_sync: n - 31 entries (device). Returns n - 31, < 0 on error. */
     int64_t sdhip_op_generic_correlate(int device, int constellation, const int8_t *d_soft, size_t n, float *d_cor, uint8_t *d_sync);
 
+    /* ---- "ccsds_turbo_decoder" (ccsds_turbo.h) ----------------------------------------------------------------------------------------------------
+       CCSDSTurboDecoderModule::process() (src-core/pipeline/modules/ccsds/module_ccsds_turbo_decoder.cpp:139-257): BPSK soft bytes in reads of
+       F = A + n (8 base + 4) bytes (A = 64 / 96 / 128 / 192, n = 2 / 3 / 4 / 6 for rates 1/2, 1/3, 1/4, 1/6) -> the ASM correlation at every position of the
+       read, either sign (the first position of the greatest |c| wins) -> the module's slide (it moves `pos` bytes, not F - pos: a read that finds the ASM in its
+       first half decodes a buffer whose middle is stale) -> derand_ccsds_soft -> CCSDSTurbo::decode (common/codings/turbo/ccsds_turbo.cpp:156-198; log-MAP
+       BCJR in double, libs/deepspace-turbo) -> 1A CF FC 1D + base bytes where the CRC-16 of the first base - 2 bytes equals the last two.
+       Not emulated: the module's extra iteration at the end of a FILE on the previous, twice derandomised buffer. */
+    enum
+    {
+        SDHIP_CCSDS_TURBO_RATE_1_2 = 0, /* codings::turbo::turbo_rate_t, turbo/ccsds_turbo.h:22-28 */
+        SDHIP_CCSDS_TURBO_RATE_1_3 = 1,
+        SDHIP_CCSDS_TURBO_RATE_1_4 = 2,
+        SDHIP_CCSDS_TURBO_RATE_1_6 = 3
+    };
+    typedef struct sdhip_ccsds_turbo_cfg
+    {
+        int rate;       /* "turbo_rate": SDHIP_CCSDS_TURBO_RATE_* (mandatory) */
+        int base;       /* "turbo_base": 223, 446, 892 or 1115 (mandatory) */
+        int iterations; /* "turbo_iters" (mandatory), >= 1 */
+        int device;
+    } sdhip_ccsds_turbo_cfg;
+    typedef struct sdhip_ccsds_turbo_stats
+    {
+        uint64_t soft_in;      /* soft bytes consumed */
+        uint64_t reads;        /* buffers decoded */
+        uint64_t frames_out;   /* frames written (the CRC held) */
+        int locked;            /* the last read found the ASM at position 0 */
+        float cor;             /* its correlation */
+        int crc_lock;          /* the last buffer's CRC held */
+        uint32_t chain_rounds; /* speculation rounds of the frame chain (one per slide) */
+        uint32_t chain_serial; /* calls that fell back to the serial walk */
+    } sdhip_ccsds_turbo_stats;
+    typedef struct sdhip_ccsds_turbo_desc
+    {
+        uint64_t offset; /* stream position where the read started */
+        int pos;         /* where it found the ASM: the buffer is slid by pos and pos more bytes are read */
+        int swapped;     /* the correlation was negative: the floats are negated */
+        float cor;
+        int crc_ok;
+    } sdhip_ccsds_turbo_desc;
+    void sdhip_ccsds_turbo_cfg_default(sdhip_ccsds_turbo_cfg *cfg); /* rate 1/2, base 223, 10 iterations (CCSDSTurbo::decode's default) */
+    void *sdhip_ccsds_turbo_create(const sdhip_ccsds_turbo_cfg *cfg); /* NULL on error: unknown rate or base, iterations < 1 */
+    void sdhip_ccsds_turbo_destroy(void *h);
+    int sdhip_ccsds_turbo_frame_bytes(void *h); /* base + 4 */
+    /* Host-buffer path: append n soft bytes; every complete read is decoded, an incomplete one (an incomplete slide included) stays pending. */
+    int sdhip_ccsds_turbo_push(void *h, const int8_t *soft, size_t n);
+    int64_t sdhip_ccsds_turbo_pull(void *h, uint8_t *frames, size_t cap_frames);
+    /* Device-resident path: n more soft bytes in HBM -> frames in d_frames (device). Returns the frames written, < 0 on error. The output does not depend on
+       how the stream is cut into calls. */
+    int64_t sdhip_ccsds_turbo_process_dev(void *h, const int8_t *d_soft, size_t n, uint8_t *d_frames, size_t cap_frames);
+    int sdhip_ccsds_turbo_get_stats(void *h, sdhip_ccsds_turbo_stats *st);
+    /* the buffers the last push / process_dev call decoded (host table). Returns their number, which may exceed cap. */
+    int64_t sdhip_ccsds_turbo_get_descs(void *h, sdhip_ccsds_turbo_desc *out, size_t cap);
+    /* The interleaver of CCSDS 131.0-B section 6.3, 0-based: out[8 base]. Returns 8 base, < 0 for an unknown base. */
+    int sdhip_ccsds_turbo_interleaver(int base, int *out);
+    /* The attached sync marker of the rate as +-1 floats: out192. Returns its length (64 / 96 / 128 / 192), < 0 for an unknown rate. */
+    int sdhip_ccsds_turbo_asm(int rate, float *out192);
+    /* unit entries. The signed ASM correlation at every position p <= n - A of a soft stream (device): d_cor[n - A + 1]. Returns that number, < 0 on error. */
+    int64_t sdhip_op_ccsds_turbo_correlate(int device, int rate, const int8_t *d_soft, size_t n, float *d_cor);
+    /* One convcode_extrinsic pass (libconvcodes.c:355-542) of constituent code `code` (0 upper, 1 lower) per frame: d_stream = nframes streams of
+       components x (8 base + 4) doubles as turbo_decode splits them off, d_msgs = nframes a-priori arrays [2][8 base], rewritten with the extrinsic values. */
+    int sdhip_op_ccsds_turbo_bcjr(int device, int rate, int base, int code, const double *d_stream, int nframes, double *d_msgs);
+    /* CCSDSTurbo::decode (ccsds_turbo.cpp:156-198) on nframes prepared codewords of n (8 base + 4) floats (device) -> d_bits, 8 base bytes a frame, one
+       information bit per byte: what the module packs and hands to the CRC. */
+    int sdhip_op_ccsds_turbo_decode(int device, int rate, int base, int iterations, const float *d_codewords, int nframes, uint8_t *d_bits);
+
     /* ---- misc ------------------------------------------------------------------------ */
     const char *sdhip_last_error(void);
     const char *sdhip_version(void);

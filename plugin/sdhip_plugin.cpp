@@ -1878,6 +1878,131 @@ namespace sdhip_plugin
         }
     };
 
+    // ------------------------------------------------------------------------------------------------ ccsds_turbo_decoder
+    // CCSDSTurboDecoderModule (src-core/pipeline/modules/ccsds/module_ccsds_turbo_decoder.{h,cpp}) on sdhip_ccsds_turbo_* (csrc/ccsds_turbo.h): the same three
+    // mandatory keys with the module's own exception texts, .soft file / fifo in, .cadu out (1A CF FC 1D + turbo_base bytes where the CRC holds). "hip_devices"
+    // stays on the CPU module.
+    class CCSDSTurboDecoderHipModule : public base::FileStreamToFileStreamModule
+    {
+        sdhip_ccsds_turbo_cfg cfg;
+        void *h = nullptr;
+        std::atomic<float> cor{0};
+        std::atomic<int> locked{0}, crc_lock{0};
+        uint64_t file_bytes = 0, file_pos = 0;
+        size_t read_bytes = 0;
+
+    public:
+        CCSDSTurboDecoderHipModule(std::string input_file, std::string output_file_hint, nlohmann::json parameters)
+            : base::FileStreamToFileStreamModule(input_file, output_file_hint, parameters)
+        {
+            std::string why;
+            if (!covers(parameters, why))
+                throw satdump_exception("ccsds_turbo_decoder_hip: " + why);
+            sdhip_ccsds_turbo_cfg_default(&cfg);
+            if (parameters.contains("turbo_rate")) // module_ccsds_turbo_decoder.cpp:20-36, 118-119
+            {
+                const std::string r = parameters["turbo_rate"].get<std::string>();
+                cfg.rate = r == "1/2" ? SDHIP_CCSDS_TURBO_RATE_1_2 : (r == "1/3" ? SDHIP_CCSDS_TURBO_RATE_1_3 : (r == "1/4" ? SDHIP_CCSDS_TURBO_RATE_1_4 : (r == "1/6" ? SDHIP_CCSDS_TURBO_RATE_1_6 : -1)));
+            }
+            else
+                throw satdump_exception("Turbo Rate is required!");
+            if (parameters.contains("turbo_base"))
+                cfg.base = parameters["turbo_base"].get<int>();
+            else
+                throw satdump_exception("Turbo Base is required!");
+            if (parameters.contains("turbo_iters"))
+                cfg.iterations = parameters["turbo_iters"].get<int>();
+            else
+                throw satdump_exception("Turbo Iters is required!");
+            if (!(cfg.base == 223 || cfg.base == 446 || cfg.base == 892 || cfg.base == 1115))
+                throw satdump_exception("Turbo Base must be 223, 446, 892 or 1115!");
+            if (cfg.rate < 0)
+                throw satdump_exception("Invalid Turbo Rate!");
+            opt(parameters, "hip_device", cfg.device);
+            static const int asm_size[4] = {64, 96, 128, 192}, wire[4] = {2, 3, 4, 6};
+            read_bytes = (size_t)asm_size[cfg.rate] + (size_t)wire[cfg.rate] * (cfg.base * 8 + 4); // d_frame_size
+            fsfsm_file_ext = ".cadu";
+        }
+        ~CCSDSTurboDecoderHipModule()
+        {
+            if (h)
+                sdhip_ccsds_turbo_destroy(h);
+        }
+        static bool covers(const nlohmann::json &p, std::string &why)
+        {
+            if (p.count("hip_devices") > 0)
+            {
+                why = "hip_devices: the turbo decoder is not sharded";
+                return false;
+            }
+            return true;
+        }
+        void init()
+        {
+            base::FileStreamToFileStreamModule::init();
+            h = sdhip_ccsds_turbo_create(&cfg);
+            if (!h)
+                throw satdump_exception(std::string("ccsds_turbo_decoder_hip: ") + sdhip_last_error());
+            if (input_data_type == DATA_FILE)
+                file_bytes = (uint64_t)std::filesystem::file_size(d_input_file);
+        }
+        void process()
+        {
+            // the module reads one buffer per iteration, plus the slide's extra bytes; here a file goes to the device in batches of 256 buffers' worth, a fifo
+            // buffer by buffer. An incomplete last read is dropped; the module's extra iteration on the stale buffer at the end of a file is not made.
+            const size_t chunk = read_bytes * (input_data_type == DATA_FILE ? 256 : 1);
+            const size_t fb = (size_t)sdhip_ccsds_turbo_frame_bytes(h);
+            std::vector<int8_t> soft(chunk);
+            std::vector<uint8_t> frames(fb * 300);
+            while (should_run())
+            {
+                size_t got = chunk;
+                if (input_data_type == DATA_FILE)
+                {
+                    got = (size_t)std::min<uint64_t>(chunk, file_bytes > file_pos ? file_bytes - file_pos : 0);
+                    file_pos += got;
+                }
+                read_data((uint8_t *)soft.data(), chunk);
+                if (got == 0)
+                    break;
+                if (sdhip_ccsds_turbo_push(h, soft.data(), got) < 0)
+                    throw satdump_exception(std::string("ccsds_turbo_decoder_hip: ") + sdhip_last_error());
+                for (;;)
+                {
+                    const int64_t n = sdhip_ccsds_turbo_pull(h, frames.data(), frames.size() / fb);
+                    if (n < 0)
+                        throw satdump_exception(std::string("ccsds_turbo_decoder_hip: ") + sdhip_last_error());
+                    if (n == 0)
+                        break;
+                    write_data(frames.data(), (size_t)n * fb);
+                }
+                sdhip_ccsds_turbo_stats st;
+                sdhip_ccsds_turbo_get_stats(h, &st);
+                locked = st.locked;
+                cor = st.cor;
+                crc_lock = st.crc_lock;
+            }
+            cleanup();
+        }
+        void drawUI(bool) {}
+        nlohmann::json getModuleStats()
+        { // (the CPU module publishes no statistics of its own; these are its three UI values)
+            auto v = base::FileStreamToFileStreamModule::getModuleStats();
+            v["correlator_lock"] = locked.load() != 0;
+            v["correlator_corr"] = cor.load();
+            v["crc_lock"] = crc_lock.load() != 0;
+            v["lock_state"] = locked.load() ? "SYNCED" : "NOSYNC";
+            return v;
+        }
+        static std::string getID() { return "ccsds_turbo_decoder_hip"; }
+        virtual std::string getIDM() { return getID(); }
+        static nlohmann::json getParams() { return {}; }
+        static std::shared_ptr<ProcessingModule> getInstance(std::string input_file, std::string output_file_hint, nlohmann::json parameters)
+        {
+            return std::make_shared<CCSDSTurboDecoderHipModule>(input_file, output_file_hint, parameters);
+        }
+    };
+
     // ------------------------------------------------------------------------------------------------ dvbs2_ts_extractor
     // S2TStoTCPModule (plugins/dvb_support/dvbs2/module_s2_ts_extractor.{h,cpp}) on sdhip_s2_ts_* (csrc/dvbs2_ts.hip): same keys ("bb_size", or "modcod" mandatory +
     // "shortframes" / "pilots" -> BBFrameBCH::dataSize(), :24-52, the same exception text), .bbframe file or fifo in, one BBFrameTSParser::work call per frame's
@@ -2301,6 +2426,7 @@ namespace sdhip_plugin
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, FengyunAHRPTDecoderHipModule);
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, FengyunMPTDecoderHipModule);
             REGISTER_MODULE_EXTERNAL(evt.modules_registry, CCSDSLDPCDecoderHipModule);
+            REGISTER_MODULE_EXTERNAL(evt.modules_registry, CCSDSTurboDecoderHipModule);
         }
         static void startedHandler(const satdump::SatDumpStartedEvent &)
         {
@@ -2397,6 +2523,19 @@ namespace sdhip_plugin
                             return cpu(in, out, p);
                         }
                         return CCSDSLDPCDecoderHipModule::getInstance(in, out, p);
+                    };
+                }
+                else if (e.id == "ccsds_turbo_decoder")
+                { // every rate and base; hip_devices stays on the CPU module
+                    auto cpu = e.inst;
+                    e.inst = [cpu](std::string in, std::string out, nlohmann::json p) -> std::shared_ptr<ProcessingModule> {
+                        std::string why;
+                        if (!CCSDSTurboDecoderHipModule::covers(p, why))
+                        {
+                            logger->info("sdhip_support: ccsds_turbo_decoder stays on the CPU module for this run (" + why + ")");
+                            return cpu(in, out, p);
+                        }
+                        return CCSDSTurboDecoderHipModule::getInstance(in, out, p);
                     };
                 }
                 else if (e.id == "ccsds_simple_psk_decoder")

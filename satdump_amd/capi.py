@@ -129,6 +129,23 @@ class CcsdsLdpcDesc(C.Structure):
 # codings::ldpc::ldpc_rate_t (common/codings/ldpc/ccsds_ldpc.h:10-16)
 CCSDS_LDPC_RATES = {"1/2": 0, "2/3": 1, "4/5": 2, "7/8": 3}
 
+class CcsdsTurboCfg(C.Structure):
+    """sdhip_ccsds_turbo_cfg (include/sdhip.h): the JSON keys of ccsds_turbo_decoder."""
+    _fields_ = [("rate", C.c_int), ("base", C.c_int), ("iterations", C.c_int), ("device", C.c_int)]
+
+
+class CcsdsTurboStats(C.Structure):
+    _fields_ = [("soft_in", C.c_uint64), ("reads", C.c_uint64), ("frames_out", C.c_uint64), ("locked", C.c_int), ("cor", C.c_float), ("crc_lock", C.c_int),
+                ("chain_rounds", C.c_uint32), ("chain_serial", C.c_uint32)]
+
+
+class CcsdsTurboDesc(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("pos", C.c_int), ("swapped", C.c_int), ("cor", C.c_float), ("crc_ok", C.c_int)]
+
+
+# codings::turbo::turbo_rate_t (common/codings/turbo/ccsds_turbo.h:22-28)
+CCSDS_TURBO_RATES = {"1/2": 0, "1/3": 1, "1/4": 2, "1/6": 3}
+
 # dvbs2_code_rate_t (common/codings/dvb-s2/dvbs2.h:9-23)
 S2_RATES = {"1/4": 0, "1/3": 1, "2/5": 2, "1/2": 3, "3/5": 4, "2/3": 5, "3/4": 6, "4/5": 7, "5/6": 8, "7/8": 9, "8/9": 10, "9/10": 11}
 
@@ -311,6 +328,26 @@ def lib():
             L.sdhip_ccsds_ldpc_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
             L.sdhip_op_ccsds_ldpc_decode.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
             L.sdhip_op_ldpc_generic_decode.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sdhip_ccsds_turbo_create"):
+            L.sdhip_ccsds_turbo_cfg_default.argtypes = [C.POINTER(CcsdsTurboCfg)]
+            L.sdhip_ccsds_turbo_create.restype = C.c_void_p
+            L.sdhip_ccsds_turbo_create.argtypes = [C.POINTER(CcsdsTurboCfg)]
+            L.sdhip_ccsds_turbo_destroy.argtypes = [C.c_void_p]
+            L.sdhip_ccsds_turbo_frame_bytes.argtypes = [C.c_void_p]
+            L.sdhip_ccsds_turbo_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.sdhip_ccsds_turbo_pull.restype = C.c_int64
+            L.sdhip_ccsds_turbo_pull.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.sdhip_ccsds_turbo_process_dev.restype = C.c_int64
+            L.sdhip_ccsds_turbo_process_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+            L.sdhip_ccsds_turbo_get_stats.argtypes = [C.c_void_p, C.POINTER(CcsdsTurboStats)]
+            L.sdhip_ccsds_turbo_get_descs.restype = C.c_int64
+            L.sdhip_ccsds_turbo_get_descs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.sdhip_ccsds_turbo_interleaver.argtypes = [C.c_int, C.c_void_p]
+            L.sdhip_ccsds_turbo_asm.argtypes = [C.c_int, C.c_void_p]
+            L.sdhip_op_ccsds_turbo_correlate.restype = C.c_int64
+            L.sdhip_op_ccsds_turbo_correlate.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.sdhip_op_ccsds_turbo_bcjr.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+            L.sdhip_op_ccsds_turbo_decode.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
             L.sdhip_op_generic_correlate.restype = C.c_int64
             L.sdhip_op_generic_correlate.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.sdhip_prof_enable.argtypes = [C.c_int]
@@ -680,3 +717,68 @@ class CcsdsLdpc:
         out = np.zeros(lib().sdhip_ccsds_ldpc_schedule(self.h, None, 0), dtype=np.uint16)
         lib().sdhip_ccsds_ldpc_schedule(self.h, out.ctypes.data_as(C.c_void_p), len(out))
         return out
+
+
+def ccsds_turbo_cfg(**kw) -> CcsdsTurboCfg:
+    """sdhip_ccsds_turbo_cfg_default plus the given keys; rate may be the JSON string ("1/2", "1/3", "1/4", "1/6")."""
+    c = CcsdsTurboCfg()
+    lib().sdhip_ccsds_turbo_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        if k == "rate" and isinstance(v, str):
+            v = CCSDS_TURBO_RATES.get(v, -1)  # (an unknown string is refused by create, with the module's message)
+        setattr(c, k, v)
+    return c
+
+
+class CcsdsTurbo:
+    """ccsds_turbo_decoder on one GPU stream (include/sdhip.h, sdhip_ccsds_turbo_*): BPSK soft bytes in, 1A CF FC 1D + base bytes out where the CRC holds."""
+
+    def __init__(self, cfg: CcsdsTurboCfg):
+        self.cfg = cfg
+        self.h = lib().sdhip_ccsds_turbo_create(C.byref(cfg))
+        if not self.h:
+            raise SdhipError(f"sdhip_ccsds_turbo_create failed: {last_error()}")
+        self.frame_bytes = lib().sdhip_ccsds_turbo_frame_bytes(self.h)
+
+    def close(self):
+        if self.h:
+            lib().sdhip_ccsds_turbo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, soft: np.ndarray):
+        soft = np.ascontiguousarray(soft, dtype=np.int8)
+        _check(lib().sdhip_ccsds_turbo_push(self.h, soft.ctypes.data_as(C.c_void_p), soft.size), "sdhip_ccsds_turbo_push")
+
+    def pull(self, max_frames: int = 1 << 12) -> np.ndarray:
+        out = np.empty((max_frames, self.frame_bytes), dtype=np.uint8)
+        n = _check(lib().sdhip_ccsds_turbo_pull(self.h, out.ctypes.data_as(C.c_void_p), max_frames), "sdhip_ccsds_turbo_pull")
+        return out[:n].copy()
+
+    def process_dev(self, d_soft_ptr: int, n: int, d_frames_ptr: int, cap_frames: int) -> int:
+        return _check(lib().sdhip_ccsds_turbo_process_dev(self.h, d_soft_ptr, n, d_frames_ptr, cap_frames), "sdhip_ccsds_turbo_process_dev")
+
+    def stats(self) -> CcsdsTurboStats:
+        st = CcsdsTurboStats()
+        lib().sdhip_ccsds_turbo_get_stats(self.h, C.byref(st))
+        return st
+
+    def descs(self) -> np.ndarray:
+        """the buffers of the last push / process_dev call: a structured array (offset, pos, swapped, cor, crc_ok)"""
+        dt = np.dtype([("offset", np.uint64), ("pos", np.int32), ("swapped", np.int32), ("cor", np.float32), ("crc_ok", np.int32)])
+        n = lib().sdhip_ccsds_turbo_get_descs(self.h, None, 0)
+        out = np.zeros(n, dtype=dt)
+        if n:
+            lib().sdhip_ccsds_turbo_get_descs(self.h, out.ctypes.data_as(C.c_void_p), n)
+        return out
+
+
+def ccsds_turbo_interleaver(base: int) -> np.ndarray:
+    out = np.zeros(base * 8, dtype=np.int32)
+    _check(lib().sdhip_ccsds_turbo_interleaver(base, out.ctypes.data_as(C.c_void_p)), "sdhip_ccsds_turbo_interleaver")
+    return out

@@ -656,3 +656,5 @@ extern "C"
 
 // ccsds_ldpc_decoder ("ldpc_rate": "7/8"): kernels, engine and C ABI
 #include "ccsds_ldpc.h"
+// ccsds_turbo_decoder: kernels, engine and C ABI
+#include "ccsds_turbo.h"
