@@ -15,6 +15,8 @@ import pytest
 gpu = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "turbo")
 STREAMS = ["r12_b223", "r13_b223", "r14_b223", "r16_b223"]
+# five frames of a longer block each, inside the waterfall, turbo_iters = 5: what they emit depends on the iteration count (test_stream_needs_its_iterations)
+LONG_STREAMS = ["r13_b446", "r14_b892", "r12_b1115"]
 BACKEND = "gpu"  # the twin's collection sets "twin"
 # max |ours - fixture| / max(1, |fixture|) over the two BCJR fixtures as first measured on an MI355X (profiles/ccsds_turbo_bench.json); the test
 # allows 16 times that, and never more than 1e-9
@@ -66,9 +68,9 @@ def _cfg(capi, g, **over):
     return capi.ccsds_turbo_cfg(**kw)
 
 
-def _run(torch, capi, g, bounds):
+def _run(torch, capi, g, bounds, **over):
     """the fixture's stream through a fresh handle in the calls `bounds` cuts it into: (output bytes, descriptors, statistics)"""
-    dec = capi.CcsdsTurbo(_cfg(capi, g))
+    dec = capi.CcsdsTurbo(_cfg(capi, g, **over))
     F = g["params"]["F"]
     d_x = _dev(torch, g["soft"])
     out, descs = [], []
@@ -188,7 +190,8 @@ def _unit_decode(torch, capi, rate, base, iterations, soft):
 @pytest.mark.parametrize("tag,rate,base", UNIT)
 def test_unit_decode(torch_cuda, capi, tag, rate, base, iterations):
     """CCSDSTurbo::decode's bits in front of the CRC gate: identical wherever the reference decodes a CRC-good frame (the transmitted one); for a codeword it does
-    not decode, the number of differing bits is printed"""
+    not decode, the number of differing bits is printed -- and on the host twin, whose arithmetic is the reference's, that number is held to 0 as well. (On the
+    GPU the bits of codewords inside the waterfall are held by tests/test_ccsds_turbo_waterfall_gpu.py, wherever the reference's own bits are stable.)"""
     u = _golden("turbo_unit")
     want = np.unpackbits(np.asarray(u[f"{tag}_bits_{iterations}"]), axis=1)
     sent = np.asarray(u[tag + "_sent"])
@@ -198,7 +201,7 @@ def test_unit_decode(torch_cuda, capi, tag, rate, base, iterations):
     for k in range(len(want)):
         diff = int((bits[k] != want[k]).sum())
         print(f"{tag}[{k}] after {iterations} iterations: the reference decodes the transmitted frame: {bool(good[k])}; {diff} of {base * 8} bits differ from the reference's")
-        if good[k]:
+        if good[k] or BACKEND == "twin":
             assert diff == 0, (tag, k, diff)
 
 
@@ -213,28 +216,32 @@ def test_unit_decode_rails(torch_cuda, capi):
 
 
 @gpu
-@pytest.mark.parametrize("name", STREAMS)
+@pytest.mark.parametrize("name", STREAMS + LONG_STREAMS)
 def test_stream_one_call(torch_cuda, capi, name):
     g = _golden(name)
     _check(g, *_run(torch_cuda, capi, g, [0, len(g["soft"])]))
 
 
 @gpu
-@pytest.mark.parametrize("name", STREAMS)
+@pytest.mark.parametrize("name", STREAMS + LONG_STREAMS)
 def test_stream_three_calls(torch_cuda, capi, name):
     g = _golden(name)
     n = len(g["soft"])
     _check(g, *_run(torch_cuda, capi, g, [0, n // 3 + 17, 2 * n // 3 + 401, n]))
 
 
+def _ragged(g):
+    """empty, 1-byte and F - 1-byte calls in between (in stream order: the five-frame streams end before 4 F + 100 + n // 2)"""
+    n, F = len(g["soft"]), g["params"]["F"]
+    return sorted([0, 0, 1, F, F, 2 * F - 1, 2 * F, 4 * F + 100, 4 * F + 101, n // 2, n // 2 + F - 1, n - 1, n, n])
+
+
 @gpu
-@pytest.mark.parametrize("name", STREAMS)
+@pytest.mark.parametrize("name", STREAMS + LONG_STREAMS)
 def test_stream_ragged_calls(torch_cuda, capi, name):
     """empty, 1-byte and F - 1-byte calls in between: an incomplete read, and an incomplete slide, stay pending"""
     g = _golden(name)
-    n, F = len(g["soft"]), g["params"]["F"]
-    b = [0, 0, 1, F, F, 2 * F - 1, 2 * F, 4 * F + 100, 4 * F + 101, n // 2, n // 2 + F - 1, n - 1, n, n]
-    _check(g, *_run(torch_cuda, capi, g, b))
+    _check(g, *_run(torch_cuda, capi, g, _ragged(g)))
 
 
 @gpu

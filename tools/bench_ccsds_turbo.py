@@ -170,6 +170,22 @@ def bcjr_error(torch, capi) -> dict:
     return out
 
 
+def bcjr_late_error(torch, capi) -> dict:
+    """the same measure over the late-iteration passes of turbo_iter_r*.npz (the iteration before a frame's first clean one, and iteration 8), teacher-forced"""
+    out = {}
+    for tag, rate in (("r12", "1/2"), ("r13", "1/3"), ("r14", "1/4"), ("r16", "1/6")):
+        g = np.load(os.path.join(ROOT, "tests", "golden", "turbo", f"turbo_iter_{tag}.npz"))
+        p, worst = g["passes"], 0.0
+        for x in range(2):
+            for code, stream, start, want in ((0, g["stream0"], p[x, 0], p[x, 1]), (1, g["stream1"], p[x, 2], p[x, 3])):
+                d_s, d_m = torch.from_numpy(np.array(stream)).cuda(), torch.from_numpy(np.array(start)).cuda()
+                assert capi.lib().sdhip_op_ccsds_turbo_bcjr(0, capi.CCSDS_TURBO_RATES[rate], 223, code, d_s.data_ptr(), 1, d_m.data_ptr()) == 0, capi.last_error()
+                worst = max(worst, float(np.max(np.abs(d_m.cpu().numpy() - want) / np.maximum(1.0, np.abs(want)))))
+        out["turbo_iter_" + tag] = worst
+    out["max"] = max(out.values())
+    return out
+
+
 def gpu(args) -> dict:
     import torch
     assert torch.cuda.is_available(), "tools/bench_ccsds_turbo.py measures on the GPU: no device, no figure"
@@ -177,7 +193,8 @@ def gpu(args) -> dict:
     from satdump_amd import capi
     L = capi.lib()
     L.sdhip_pool_enable(1)
-    res = {"device": torch.cuda.get_device_name(0), "frames": args.frames, "reps": args.reps, "warmup": args.warmup, "bcjr_message_error": bcjr_error(torch, capi)}
+    res = {"device": torch.cuda.get_device_name(0), "frames": args.frames, "reps": args.reps, "warmup": args.warmup, "bcjr_message_error": bcjr_error(torch, capi),
+           "bcjr_late_message_error": bcjr_late_error(torch, capi)}
     for key, (rate, base, iters) in SETTINGS.items():
         soft = make_stream(rate, base, capi.ccsds_turbo_interleaver(base).astype(np.int64))
         tiles = max(1, args.frames // DISTINCT)

@@ -8,6 +8,8 @@
 // memmove(buf, buf + pos, pos) reads past its buffer when pos > F / 2; the bytes it fetches there are overwritten by the second read, so the restatement moves
 // min(pos, F - pos) bytes and arrives at the same buffer. The module's last iteration at the end of a file (the previous buffer decoded again after a second
 // derandomisation) is not restated.
+// turboref_iterate restates turbo_decode's loop (libturbocodes.c:160-186) over convcode_extrinsic, so that the bits after every iteration and the a-priori arrays
+// around each pass can be recorded, and so that the messages can be perturbed between the passes (which tells the decisions that hang on the last bits of exp / log).
 // Built with -fno-access-control (d_pi, d_turbo and puncturing() are private) and -Dvolk_8i_s32f_convert_32f=volk_8i_s32f_convert_32f_u (the shim's name for
 // VOLK's generic kernel).
 #include <algorithm>
@@ -278,5 +280,66 @@ extern "C"
         convcode_extrinsic(streams[1].data(), (double)streams[1].size(), &messages, t.d_turbo.lower_code, nv, 0);
         memcpy(after_lower, m0.data(), L * sizeof(double));
         memcpy(after_lower + L, m1.data(), L * sizeof(double));
+    }
+    // turbo_decode's loop (libturbocodes.c:160-186) by hand over convcode_extrinsic, on one prepared codeword. The lower pass is asked for its decision in every
+    // iteration (the decision reads the arrays and changes none), so bits[k - 1][L] is what turbo_decode returns for `iterations` = k, for every k <= iters.
+    // rec[0], rec[1]: two iterations (1-based, 0 = none) whose passes are recorded to passes[x][4][2][L]: the a-priori arrays the upper pass receives and
+    // leaves, and the ones the lower pass receives (interleaved) and leaves (before message_deinterleave). stream0 / stream1 (may be null): the two constituent
+    // streams. perturb != 0: after every pass each message m becomes m + s * 2^-43 * max(1, |m|), s = +-1 from a generator seeded with `perturb`.
+    void turboref_iterate(int rate, int base, const float *cw, int iters, uint8_t *bits, const int *rec, double *passes, double *stream0, double *stream1, uint64_t perturb)
+    {
+        CCSDSTurbo t((codings::turbo::turbo_base_t)base, (codings::turbo::turbo_rate_t)rate);
+        std::vector<double> streams[2];
+        split(t, cw, streams);
+        if (stream0)
+            memcpy(stream0, streams[0].data(), streams[0].size() * sizeof(double));
+        if (stream1)
+            memcpy(stream1, streams[1].data(), streams[1].size() * sizeof(double));
+        const int L = base * 8;
+        std::vector<double> m0(L, log(0.5)), m1(L, log(0.5));
+        double *rows[2] = {m0.data(), m1.data()};
+        double **messages = rows;
+        const double nv = t.d_sigma * t.d_sigma;
+        uint64_t x = perturb;
+        auto shake = [&]() {
+            if (!perturb)
+                return;
+            for (int r = 0; r < 2; r++)
+                for (int i = 0; i < L; i++)
+                {
+                    x += 0x9E3779B97F4A7C15ull; // splitmix64
+                    uint64_t z = x;
+                    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                    z ^= z >> 31;
+                    const double m = rows[r][i];
+                    rows[r][i] = m + ((z >> 63) ? 1.0 : -1.0) * ldexp(1.0, -43) * std::max(1.0, fabs(m));
+                }
+        };
+        auto record = [&](int it, int which) {
+            for (int k = 0; k < 2; k++)
+                if (passes && rec && rec[k] == it + 1)
+                {
+                    double *p = passes + ((size_t)k * 4 + which) * 2 * L;
+                    memcpy(p, m0.data(), L * sizeof(double));
+                    memcpy(p + L, m1.data(), L * sizeof(double));
+                }
+        };
+        for (int it = 0; it < iters; it++)
+        {
+            record(it, 0);
+            free(convcode_extrinsic(streams[0].data(), (double)streams[0].size(), &messages, t.d_turbo.upper_code, nv, 0));
+            record(it, 1);
+            shake();
+            message_interleave(&messages, t.d_turbo);
+            record(it, 2);
+            int *decoded = convcode_extrinsic(streams[1].data(), (double)streams[1].size(), &messages, t.d_turbo.lower_code, nv, 1);
+            record(it, 3);
+            for (int i = 0; i < L; i++) // turbo_deinterleave
+                bits[(size_t)it * L + t.d_pi[i]] = decoded[i] ? 1 : 0;
+            free(decoded);
+            shake();
+            message_deinterleave(&messages, t.d_turbo);
+        }
     }
 }
