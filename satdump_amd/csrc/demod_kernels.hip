@@ -7,6 +7,7 @@
 // reference bit for bit (tests/test_demod_gpu.py, exact mode).
 #include "demod_kernels.h"
 #include "glibc_atan2f.h"
+#include <atomic>
 #include <climits>
 #include <optional>
 #include <type_traits>
@@ -2415,9 +2416,11 @@ namespace sdhip
     constexpr int MM_RING = 32;    // Gardner lanes (their window reaches up to MM_BACK_MAX samples further back)
     constexpr int MM_RING_MM = 16; // Mueller & Mueller lanes: a window [inc-7, inc] with inc in the newest block lies inside the last 16 samples; 11.5 KB of ring
                                    // + 4 KB of interpolator arms per wave lets a CU hold eight blocks -- two waves on every SIMD (it was six: one and a half)
-    // The symbol loop runs once per FEED samples (k_mm's FEED: 8 or 16). A feed moves FEED / 8 blocks into the ring first, so a window [inc-7, inc] with
-    // inc >= the feed's first sample reaches FEED + 7 samples back from the newest: the ring holds at least FEED + 8 slots (a power of two for the slot mask)
-    constexpr int mm_ring_mm(const int feed) { return feed == 8 ? MM_RING_MM : 32; }
+    // The symbol loop runs once per FEED samples (k_mm's FEED: 8, 16 or 32). A feed moves FEED / 8 blocks into the ring first, so a window [inc-7, inc] with
+    // inc >= the feed's first sample reaches FEED + 7 samples back from the newest: the ring holds at least FEED + 8 slots (a power of two for the slot mask):
+    // 16, 32 (24 would do), 64 (40 would do: with the mirror and the arms 40 448 bytes of LDS per block, four blocks to a CU -- launch_mm's occupancy rule)
+    constexpr int mm_ring_mm(const int feed) { return feed == 8 ? MM_RING_MM : feed == 16 ? 32 : 64; }
+    static_assert(mm_ring_mm(8) >= 8 + 8 && mm_ring_mm(16) >= 16 + 8 && mm_ring_mm(32) >= 32 + 8, "the ring holds a feed and the 8-sample window in front of it");
     // ring[slot][lane]: slot-major, so lane l of a 32-lane LDS access group always owns 8-byte bank pair l whatever slot it
     // addresses -- the lanes' windows sit at unrelated ring positions, and a lane-major layout made them collide at random
     // (SQ: bank-conflict cycles were twice the active LDS cycles)
@@ -2478,7 +2481,7 @@ namespace sdhip
                 f.prev_im = t;
             }
             f.ring[(slot + j) * MM_RING_STRIDE] = v;
-            if (j < MM_MIRROR && slot == 0)
+            if (j < MM_MIRROR && slot == 0) // (any RING that is a multiple of 8: a block never straddles the ring's end, the mirror sits behind slot RING - 1)
                 f.ring[(RING + j) * MM_RING_STRIDE] = v;
         }
         f.next = i + 8;
@@ -2754,7 +2757,8 @@ namespace sdhip
                        MM_TAP = 32,     // tests only: arm positions in place of the symbols (MmParams::tap, sdhip_demod_set_tap)
                        MM_LIN = 64,     // ndsp::MMClockRecoveryFastBlock's loop on one sequential lane (MmParams::loop == 2)
                        MM_FEED16 = 128, // the symbol loop runs once per 16 samples instead of 8 (the M&M instances with checkpoints; SDHIP_MM_FEED=8 and SDHIP_COOP_MM=1 keep 8)
-                       MM_UNR = 256;    // the fast paths run three symbols per pass through mm_sym (with MM_FEED16; SDHIP_MM_LOOP=0 keeps the one-symbol loop)
+                       MM_UNR = 256,    // the fast paths run three symbols per pass through mm_sym (with MM_FEED16 or MM_FEED32; SDHIP_MM_LOOP=0 keeps the one-symbol loop)
+                       MM_FEED32 = 512; // the symbol loop runs once per 32 samples (instead of MM_FEED16, under its restrictions; a 64-slot ring: see launch_mm's occupancy rule)
     // CKPT: whenever the block ending at a multiple of MM_CK_SAMPLES samples into its chunk has been fed, a lane leaves a
     // checkpoint {mu, omega, inc, symbols so far}. A re-run lane (exact start state) compares itself with the checkpoint at the
     // same position and stops as soon as it has produced the same number of symbols and is inside the boundary tolerance in
@@ -2765,8 +2769,8 @@ namespace sdhip
     // SPLIT (experimental, SDHIP_MM_SPLIT=1, same results bit for bit -- checked on the host twin; not yet measured): the symbol loop
     // as three plain loops, one per phase, each bounded by a single sample-index test, instead of one loop that re-evaluates the
     // warm-up / chunk / look-ahead bookkeeping (~45 of its ~200 instructions) on every symbol. The lane is issue-bound.
-    // FEED: samples moved into the ring per pass of the symbol loop (see block_body / feed_body below): 8, or 16 for the chunk-parallel M&M instances the
-    // timed step runs (SDHIP_MM_FEED=8 for A/B; the cooperative loads, Gardner, LIN and the tap keep 8)
+    // FEED: samples moved into the ring per pass of the symbol loop (see block_body / feed_body below): 8, or 16 or 32 for the chunk-parallel M&M instances the
+    // timed step runs (SDHIP_MM_FEED=8 / 16 and SDHIP_MM_FEED32=0 / 1 for A/B; the cooperative loads, Gardner, LIN and the tap keep 8)
     // UNR: the wave-uniform fast paths run their symbols three at a time through mm_sym, without the per-symbol state rotation (the 16-sample feeds'
     // M&M instances; SDHIP_MM_LOOP=0 keeps the one-symbol loop for A/B)
     template <unsigned V>
@@ -2775,13 +2779,19 @@ namespace sdhip
                                                float ck_tol, int coop_nb)
     {
         constexpr bool CKPT = V & MM_CKPT, SPLIT = V & MM_SPLIT, Q8 = V & MM_Q8, FAST = V & MM_FAST, GARD = V & MM_GARD, TAP = V & MM_TAP, LIN = V & MM_LIN, UNR = V & MM_UNR;
-        constexpr int FEED = (V & MM_FEED16) ? 16 : 8;
-        static_assert(!(V & MM_FEED16) || (!GARD && !LIN && !SPLIT), "MM_FEED16: the M&M instances only");
-        static_assert(!UNR || ((V & MM_FEED16) && !TAP), "MM_UNR: the M&M instances with MM_FEED16");
+        constexpr int FEED = (V & MM_FEED32) ? 32 : (V & MM_FEED16) ? 16 : 8;
+        static_assert(!(V & MM_FEED16) || !(V & MM_FEED32), "MM_FEED16 or MM_FEED32, not both");
+        static_assert(FEED == 8 || (CKPT && !GARD && !LIN && !SPLIT && !TAP), "MM_FEED16 / MM_FEED32: the M&M instances with checkpoints only");
+        static_assert(!UNR || (FEED > 8 && !TAP), "MM_UNR: the M&M instances with MM_FEED16 or MM_FEED32");
+        // at most ONE checkpoint block ends inside a feed (feed_body): the checkpoints lie a whole number of feeds apart
+        static_assert(MM_CK_SAMPLES % FEED == 0, "feed_body handles one checkpoint per feed");
         static_assert(!SPLIT || !CKPT, "MM_SPLIT: without MM_CKPT");
         static_assert(!TAP || (CKPT && FAST && !Q8), "MM_TAP: the default float-row instance (MM_CKPT | MM_FAST) only");
         static_assert(!LIN || V == MM_LIN, "MM_LIN: no other flag");
         constexpr int RING = GARD ? MM_RING : mm_ring_mm(FEED);
+        static_assert((RING & (RING - 1)) == 0 && RING >= FEED + 8, "slot masks; a feed and the window in front of it");
+        // (static LDS, ring + mirror + arms: 15 872 bytes with 8-sample feeds, 24 064 with 16, 40 448 with 32)
+        static_assert(sizeof(cf32) * (RING + MM_MIRROR) * MM_RING_STRIDE + 4096 <= (FEED == 32 ? 40448 : 24064), "blocks per CU: launch_mm counts on these");
         __shared__ cf32 rings[(RING + MM_MIRROR) * MM_RING_STRIDE];
         __shared__ __attribute__((aligned(16))) float bank[128 * MM_ARM_STRIDE];
         // the transposition buffer of the cooperative loads (load side only: the symbols leave per lane) is DYNAMIC shared memory, there only when a launch uses it
@@ -2922,7 +2932,9 @@ namespace sdhip
         // spec, endst, the checkpoints and the per-symbol path see the state mm_iter leaves. Same steps, same order, same results.
         const auto run3 = [&](const long long to, auto chunk) __attribute__((always_inline)) {
                 constexpr bool CH = decltype(chunk)::value;
-                int rel = (int)(s.inc - to); // a window lies inside the ring: |inc - to| < 2 RING
+                // 32 bits do for any FEED: a lane that runs a symbol has to - FEED <= inc < to (every symbol in front of the last feed's end is done, or the
+                // lane started inside this feed), a lane that runs none is ahead of `to` by less than the samples of one symbol
+                int rel = (int)(s.inc - to);
                 if (rel >= 0)
                     return;
                 const int roff = (int)((to - 7) & (RING - 1)), lo = (int)(to > 0x7fffffffll ? (long long)INT_MIN : -to);
@@ -3034,6 +3046,7 @@ namespace sdhip
                     // inside its chunk for the whole block: then the symbol loop needs none of the per-symbol phase bookkeeping below (a third of its
                     // instructions; the kernel is issue-bound at two waves per SIMD). Same iterations, same order, same results.
                     const unsigned long long act = __ballot(1);
+                    // (cnt + FEED < p.cap: a symbol advances the index by a sample at least, so the at most FEED symbols in front of `to` fit the row)
                     if (__ballot(!done && phase == 1 && to <= e && cnt + FEED < p.cap) == act) // (!done: a re-run lane that merged at a checkpoint stays out)
                     {
                         if constexpr (UNR)
@@ -3110,11 +3123,12 @@ namespace sdhip
         // FEED > 8: the last FEED / 8 blocks are in the ring; every symbol whose window is complete. The checkpoint of a block inside the feed sees the
         // state the 8-sample loop leaves it (every symbol in front of that block done): the symbol loop stops there first. Same iterations, same order,
         // same results -- the wave just runs its symbol loop over twice the samples (at MetOp's 2.57 samples a symbol a lane finds 3 or 4 symbols in 8
-        // samples, and the wave runs 4: 22 % of the slots idle; 6.2 of 7 in 16 samples)
+        // samples, and the wave runs 4: 22 % of the slots idle; 6.2 of 7 in 16 samples, 12.4 of 13 in 32)
         const auto feed_body = [&]() __attribute__((always_inline)) {
                 long long to = f.next, c = 0;
                 if constexpr (CKPT)
-                {
+                { // r: samples of this feed behind the last checkpoint position; r < FEED: that position is the end of one of this feed's blocks -- of one only,
+                  // MM_CK_SAMPLES being a multiple of FEED (asserted above). c - 8 may be the last feed's end (r = FEED - 8): the first run_syms finds nothing to do
                     const long long r = (f.next - b) & (MM_CK_SAMPLES - 1);
                     if (r < FEED)
                     {
@@ -3173,7 +3187,9 @@ namespace sdhip
                     block_body(cur);
                 }
                 else
-                { // the same loads at the same sample positions: a lane stops in the same pass of the while loop as with 8-sample feeds
+                { // the same loads at the same sample positions: a lane stops in the same pass of the while loop as with 8-sample feeds (mm_feed_init's floor to 16
+                  // samples stays for that reason: a pass is the same 32 samples at any FEED). A block is asked for 8 * MM_DEPTH = 32 samples before it is put, at
+                  // any FEED; with FEED = 32 the whole queue is refilled in front of one symbol loop over 32 samples instead of half of it in front of each of two
 #pragma unroll
                     for (int j = 0; j < FEED / 8; j++)
                     {
@@ -3190,6 +3206,22 @@ namespace sdhip
                 q8_flush_part();
         if (!merged) // a merged re-run leaves the chunk's count, look-ahead and end state as the speculative run wrote them
             counts[2 * k + 1] = nx;
+    }
+    // the largest main launch that takes the 32-sample feeds by default: four blocks (40 448 bytes of LDS each) to every CU of the device, asked once per device
+    static int mm_feed32_max_blocks()
+    {
+        static std::atomic<int> cus_of[64];
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+            return 0;
+        int cus = cus_of[dev].load(std::memory_order_relaxed);
+        if (cus == 0)
+        {
+            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+                cus = -1;
+            cus_of[dev].store(cus, std::memory_order_relaxed);
+        }
+        return cus > 0 ? 4 * cus : 0;
     }
     void launch_mm(const cf32 *x, cf32 *sym_scratch, int *counts, const ChunkGeom &g, const MmParams &p, const MmState *start0, MmState *spec, MmState *endst,
                    MmCert *spec_c, MmCert *end_c, const int *redo, int nredo, hipStream_t st, MmCkpt *ck, int ck_per_chunk, float ck_tol)
@@ -3235,23 +3267,46 @@ namespace sdhip
         }
         else
         {
-            // the chunk-parallel instances run their symbol loop over 16-sample feeds (SDHIP_MM_FEED=8: over every 8-sample block, as before; same results
-            // bit for bit); the cooperative loads keep 8
-            const int feed = coop_nb > 0 ? 8 : env_int("SDHIP_MM_FEED", 16);
+            // the chunk-parallel instances run their symbol loop over 16- or 32-sample feeds (SDHIP_MM_FEED=8: over every 8-sample block, as before; same
+            // results bit for bit at any width); the cooperative loads keep 8
+            // 32-sample feeds: the ring takes 40 448 bytes of LDS per block, so a CU holds four blocks (one wave per SIMD) where it holds six of the 16-wide
+            // ones. A main launch of at most four blocks per CU is resident at once either way and takes 32 by default; a larger one would run a second round
+            // of blocks and keeps 16, and so do the re-run launches (a few lanes).
+            // The switches: SDHIP_MM_FEED names 8 or 16 as it always did (any other value is refused) and, when set, is the width that runs;
+            // SDHIP_MM_FEED32=1 widens a main launch's 16 to 32 whatever its size, =0 never does; with neither set the rule above decides.
+            const char *feed_env = getenv("SDHIP_MM_FEED");
+            const bool feed_set = feed_env && *feed_env;
+            int feed = coop_nb > 0 ? 8 : env_int("SDHIP_MM_FEED", 16);
             if (feed != 8 && feed != 16)
-                throw HipError("SDHIP_MM_FEED: 8 or 16");
+                throw HipError("SDHIP_MM_FEED: 8 or 16 (SDHIP_MM_FEED32=1 for 32-sample feeds)");
+            const int wide_sw = env_int("SDHIP_MM_FEED32", -1);
+            if (wide_sw < -1 || wide_sw > 1)
+                throw HipError("SDHIP_MM_FEED32: 0 or 1");
+            if (wide_sw == 1 && feed_set && feed == 8 && coop_nb == 0)
+                throw HipError("SDHIP_MM_FEED32=1 with SDHIP_MM_FEED=8: one or the other");
+            if (feed == 16 && !redo && (wide_sw == 1 || (wide_sw == -1 && !feed_set && nblk <= mm_feed32_max_blocks())))
+                feed = 32;
             // their fast paths run three symbols per pass without the state rotation (SDHIP_MM_LOOP=0: one symbol per pass, as before; same results bit for bit)
             // (mm_sym clips the rate with v_med3_f32: the selects' value for a limit >= 0 -- a negative relative limit keeps the one-symbol loop)
             const int loop_sw = env_int("SDHIP_MM_LOOP", 1);
             if (loop_sw != 0 && loop_sw != 1)
                 throw HipError("SDHIP_MM_LOOP: 0 or 1");
             const bool unr = loop_sw == 1 && p.omega_limit >= 0.0f;
+            // the 32-wide instances are the unrolled ones of main launches (the ones that run); everything else that asks for 32 runs 16
+            if (feed == 32 && (redo || !unr || !ck))
+                feed = 16;
             if (ck)
-                v = MM_CKPT | (p.q8 ? MM_Q8 : 0) | (p.fast ? MM_FAST : 0) | (feed == 16 ? MM_FEED16 | (unr ? MM_UNR : 0) : 0);
+                v = MM_CKPT | (p.q8 ? MM_Q8 : 0) | (p.fast ? MM_FAST : 0) | (feed == 32 ? MM_FEED32 | MM_UNR : feed == 16 ? MM_FEED16 | (unr ? MM_UNR : 0) : 0);
             else // without checkpoints (exact mode, single blocks, SDHIP_CKPT=0): the 8-sample loop, unfused
                 v = p.q8 ? MM_Q8 : env_int("SDHIP_MM_SPLIT", 0) == 1 ? MM_SPLIT : 0;
         }
         const bool ckpt = v & MM_CKPT;
+        std::optional<ProfScope> _pf; // SDHIP_DEBUG: the feed width of the main launches shows in the launch counts (tests ask there which width ran)
+        if (!redo && getenv("SDHIP_DEBUG"))
+            _pf.emplace((v & MM_FEED32)   ? "k_mm (main launches over 32-sample feeds, included in k_mm)"
+                        : (v & MM_FEED16) ? "k_mm (main launches over 16-sample feeds, included in k_mm)"
+                                          : "k_mm (main launches over 8-sample feeds, included in k_mm)",
+                        st);
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(nblk), dim3(64), coop_nb > 0 ? COOP_LDS_BYTES : 0, st, x, sym_scratch, counts, g, p, start0, spec, endst, spec_c, end_c, redo, nredo,
                                ckpt ? ck : nullptr, ckpt ? ck_per_chunk : 0, ckpt ? ck_tol : 0.0f, coop_nb);
@@ -3260,13 +3315,17 @@ namespace sdhip
 #define MM_INSTANCE(V) case (V): return go(k_mm<(V)>);
         switch (v)
         {
-            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FAST | MM_FEED16 | MM_UNR) // the timed step, int8 rows
+            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FAST | MM_FEED32 | MM_UNR) // the timed step, int8 rows
+            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FEED32 | MM_UNR)
+            MM_INSTANCE(MM_CKPT | MM_FAST | MM_FEED32 | MM_UNR) // the timed step, float rows
+            MM_INSTANCE(MM_CKPT | MM_FEED32 | MM_UNR)
+            MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FAST | MM_FEED16 | MM_UNR) // (the timed step's before the 32-sample feeds; larger launches and re-runs)
             MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FAST | MM_FEED16)
             MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FAST)
             MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FEED16 | MM_UNR)
             MM_INSTANCE(MM_CKPT | MM_Q8 | MM_FEED16)
             MM_INSTANCE(MM_CKPT | MM_Q8)
-            MM_INSTANCE(MM_CKPT | MM_FAST | MM_FEED16 | MM_UNR) // the timed step, float rows
+            MM_INSTANCE(MM_CKPT | MM_FAST | MM_FEED16 | MM_UNR)
             MM_INSTANCE(MM_CKPT | MM_FAST | MM_FEED16)
             MM_INSTANCE(MM_CKPT | MM_FAST)
             MM_INSTANCE(MM_CKPT | MM_FEED16 | MM_UNR)
